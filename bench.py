@@ -2,6 +2,7 @@
 """Headline benchmark: env-steps/s of the vectorised LB environment (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--servers S]
+                    [--dump-outputs DIR] [--full]
 
 One rank per GPU: under torch.distributed.run, or, for --gpus N > 1 without it, N rank processes
 this script starts itself (same environment contract).  Weak scaling: every GPU steps its own shard of B envs
@@ -11,11 +12,21 @@ every env: random-policy actions drawn on the GPU, dynamics kernel, observe kern
 reward, done), episode bookkeeping and the masked auto-reset launch.
 
 Default N=1 workload: 65536 envs x 4 servers (north-star point; BASELINE configs[1] is the same
-random-policy rollout at 4096 envs and is a parity-test case).  Prints ONE JSON line (rank 0)
-with a `roofline` object for the dominant kernel (HIP-event timed inside the timed region), a
-`cpu_baseline` (the C oracle on host cores, bounded sample of the same workload) and, with
-`--late-episode 1000,5000` at N=1, `late_episode`: the same envs timed again at those episode steps
-(`value` stays the early-episode rate, the most expensive phase of an episode).
+random-policy rollout at 4096 envs and is a parity-test case).  Prints ONE JSON line (rank 0).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the
+`--dump-outputs` files when asked for, and the result line (`value`, `ms_per_step`, the workload's
+`config`, the per-rank times).  `--dump-outputs DIR` writes what the last timed step returned to its
+caller as DIR/<name>.npy (float32 / float64); with the same arguments the inputs, and so these
+arrays, are the same from run to run.
+
+`--full` adds every other leg to the same line: a `roofline` object for the dominant kernel
+(HIP-event timed inside the timed region, bytes from an accounting replay of the timed steps), the
+`graph` leg (the same steps replayed from a captured graph, in a child process), a `cpu_baseline`
+(the C oracle on host cores, bounded sample of the same workload) and, with `--late-episode
+1000,5000` or `--async-groups G` at N=1, `late_episode` / `async_groups`: the same envs timed again
+at those episode steps or as G stream groups (`value` stays the early-episode rate, the most
+expensive phase of an episode).
 """
 import argparse
 import ctypes
@@ -172,6 +183,17 @@ def parse():
                          "problem-04 actor on GPU (configs[3]); qmix: problem-05 agents + "
                          "mixer on GPU (configs[4])")
     ap.add_argument("--seed", type=int, default=20260109)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg and report it on the same "
+                         "line: the accounting replay and roofline, the graph leg (--no-graph "
+                         "skips it), the CPU baseline (--no-cpu-baseline skips it), and "
+                         "--late-episode / --async-groups when given.  Off by default: a plain "
+                         "run warms up, times --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its "
+                         "caller (observation, reward, done, episode statistics; the policy "
+                         "workloads' Q_tot) as DIR/<name>.npy, float32 or float64, at most 64 MB "
+                         "in all (a seeded sample of env rows beyond that); rank 0's shard")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--trace", default=None,
                     help="replay data/traces/<name>.npz (e.g. poisson_for_loop_rate_500: configs[2])")
@@ -208,7 +230,10 @@ def parse():
                          "same envs and also time --steps steps from these episode steps (comma "
                          "list, e.g. 1000,5000; off by default so a profile of the default command "
                          "covers exactly the headline steps).  Reported beside `value`, never as it")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.late_episode or args.async_groups > 1):
+        ap.error("--late-episode and --async-groups are legs of a --full run: add --full")
+    return args
 
 
 def _cpu_info():
@@ -517,6 +542,56 @@ def prewarm_scratch(args, dev, B, S, common):
                     "before the measured env exists; not part of W or K"}
 
 
+DUMP_BUDGET = 60 * 10**6  # array bytes --dump-outputs writes at most (64 MB with room to spare)
+
+
+def step_outputs(workload: str, last, ro=None) -> dict:
+    """name -> device tensor of everything the last timed step handed its caller: env.step's
+    (obs, reward, done, info) for the random-policy rollout, the rollout objects' step() results
+    (and the observation they keep for the next step) for the policy workloads."""
+    import torch
+    if workload == "rollout":
+        obs, rew, done, info = last
+        named = {"obs": obs, "reward": rew, "done": done}
+    elif workload == "sac-gru":
+        rew, done, info = last
+        named = {"obs": ro.obs, "reward": rew, "done": done}
+    else:
+        q_tot, rew, done, info = last
+        named = {"obs": ro.obs, "q_tot": q_tot, "reward": rew, "done": done}
+    for k, v in info.items():
+        if isinstance(v, torch.Tensor):
+            named["info_" + k] = v
+    return named
+
+
+def dump_outputs(path: str, named: dict, seed: int) -> dict:
+    """Write each tensor as path/<name>.npy: float64 stays float64, every other dtype (float32,
+    the int32 episode lengths, the 0/1 done flags) becomes float32, exactly.  Within DUMP_BUDGET
+    the arrays are whole; beyond it every array keeps the same sorted sample of env rows (drawn
+    once from `seed`, written as sample_rows.npy), so two runs with the same arguments write the
+    same rows.  Returns {name: shape} for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in named.items():
+        a = t.detach().cpu().numpy()
+        host[name] = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BUDGET:
+        B = max(a.shape[0] for a in host.values() if a.ndim)
+        keep = max(1, int(B * (DUMP_BUDGET - 8 * B) / total))
+        rows = np.sort(np.random.default_rng(seed).choice(B, keep, replace=False))
+        host = {n: (a[rows] if a.ndim and a.shape[0] == B else a) for n, a in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+        total = sum(a.nbytes for a in host.values())
+        if total > DUMP_BUDGET:
+            raise SystemExit(f"--dump-outputs: {total} bytes after sampling env rows")
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
+
+
 def spawn_ranks(args) -> int:
     """`bench.py --gpus N` without torchrun: start N rank processes of this script (one per GPU,
     the torchrun environment contract: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*), before this
@@ -547,6 +622,66 @@ def spawn_ranks(args) -> int:
                     q.terminate()
         time.sleep(0.2)
     return rc
+
+
+def roofline_leg(handle, lib, one_step, steps, replay, B, S, avg, names, ran, dyn, obs_name,
+                 fused):
+    """The `roofline` object of a --full run: the accounting replay of the timed steps (a run of
+    its own: step_accounting), the algorithmic bytes it implies per kernel against this run's
+    HIP-event kernel times, and the committed counter files where they apply to this work."""
+    slots, inflight = step_accounting(handle, lib, one_step, steps, replay)
+    abytes = algorithmic_bytes(S, slots / B, inflight / B,
+                               paired=True)  # duration "age", lost-FIN off: no plane
+    abytes[obs_name] = abytes.pop("observe_kernel")
+    abytes[dyn] = abytes.pop("dynamics_kernel")
+    abytes[fused] = abytes.pop("fused_step_kernel")
+    per_kernel = {}
+    for k in avg:
+        ab_k = abytes[k] * B
+        ach = ab_k / (avg[k] * 1e-3) / 1e9
+        per_kernel[k] = {"avg_launch_ms": avg[k], "algorithmic_bytes_per_launch": ab_k,
+                         "achieved_GBps": ach, "frac": ach / HBM_PEAK_GBS}
+    sigs = {names[c]: sig for c, sig in ran.items() if c in names}
+    for k in per_kernel:
+        per_kernel[k]["signature"] = sigs.get(k)
+    dom = max(avg, key=avg.get)
+    ab = abytes[dom] * B
+    achieved = ab / (avg[dom] * 1e-3) / 1e9
+    valu = valu_roofline(B, S, avg, sigs, slots / B)
+    traffic, traffic_note, traffic_workload = None, None, None
+    tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tfile):
+        t = json.load(open(tfile))
+        held = t.get("bytes_per_launch", {})
+        traffic_workload = t.get("workload")
+        if t.get("batch") != B or t.get("servers") != S:
+            traffic_note = f"profiles/pmc_traffic.json is for {t.get('batch')} x {t.get('servers')}"
+        elif sigs.get(dom) not in held:
+            traffic_note = (f"profiles/pmc_traffic.json has no counters for {sigs.get(dom)!r} "
+                            f"(it holds {sorted(held)})")
+        else:
+            traffic_note = phase_mismatch(traffic_workload, slots / B, "pmc_traffic.json")
+            if traffic_note is None:
+                traffic = held[sigs[dom]]
+    return {"bound": "hbm", "kernel": dom, "achieved": achieved,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic, "traffic_source": "profiles/pmc_traffic.json"
+            if traffic is not None else None, "stale_reason": traffic_note,
+            "traffic_workload": traffic_workload,
+            "signature": sigs.get(dom), "algorithmic_bytes_per_launch": ab,
+            "avg_launch_ms": avg[dom],
+            "kernel_avg_ms": avg, "kernels": per_kernel, "valu": valu,
+            # the two simulator kernels take about equal time: `kernel` is the longer
+            # one this run; the dynamics kernel moves few bytes by construction (an
+            # event loop, latency-bound: see `valu`), observe is the HBM-heavy one
+            "hbm_heavy_kernel": (max(per_kernel, key=lambda k: per_kernel[k]
+                                     ["algorithmic_bytes_per_launch"])
+                                 if per_kernel else None),
+            "accounting": {"reservoir_slots_written_per_env_step": slots / B,
+                           "flows_in_flight_per_env": inflight / B,
+                           "basis": "lbsim_step_stats after each step of an exact "
+                                    "replay of the timed steps" if replay else
+                                    "lbsim_step_stats over as many further steps"}}
 
 
 def main():
@@ -613,7 +748,7 @@ def main():
 
         def one_step():
             a = torch.randint(0, 3, (B, S), device=dev, dtype=torch.int64, generator=gen)
-            env.step(a)
+            return env.step(a)
     elif args.workload == "sac-gru":
         from marllb_amd.rollout import SACGRURollout
         env = VecLoadBalanceEnv(B, S, action_type="continuous", max_steps=10000, **common)
@@ -621,7 +756,7 @@ def main():
         handle = env.handle
 
         def one_step():
-            ro.step()
+            return ro.step()
     else:
         from marllb_amd.multi_agent import VecMultiAgentLoadBalanceEnv
         from marllb_amd.rollout import QMIXRollout
@@ -633,7 +768,7 @@ def main():
         handle = env.vec.handle
 
         def one_step():
-            ro.step()
+            return ro.step()
 
     replay = None
     if args.workload == "rollout" and rank == 0:  # exact accounting replay of warm-up + timed steps
@@ -659,8 +794,9 @@ def main():
         policies.profile_events = []
     handle.check(lib.lbsim_profile_begin(handle.h, 4 * args.steps + 8))
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     if dist_on:
@@ -673,12 +809,16 @@ def main():
     cdev = dev if backend == "nccl" else None
     elapsed = lbdist.max_over_ranks(t1 - t0, cdev)
     per_rank = lbdist.gather_over_ranks(t1 - t0, cdev)
+    dumped = None
+    if args.dump_outputs and rank == 0 and last is not None:
+        dumped = dump_outputs(args.dump_outputs, step_outputs(
+            args.workload, last, None if args.workload == "rollout" else ro), args.seed)
     # the graph leg right after the timed region (before the accounting replay and everything
     # else), so both legs run on the GPU in a similar state: sustained load lowers the kernels'
     # speed over the following seconds (profiles/r05k/).  In a child process: nothing the capture
     # or the replays do can abort this one (graph_leg_child).
     graph_res = None
-    if world == 1 and not args.no_graph:
+    if args.full and world == 1 and not args.no_graph:
         kms = sum(ms[i] / cnt[i] for i in (0, 1, 4) if cnt[i] > 0)
         if pol_events:
             kms += sum(a.elapsed_time(b) for a, b in pol_events) / len(pol_events)
@@ -701,40 +841,6 @@ def main():
         names = {0: dyn, 1: obs_name, 4: fused}
         avg = {names[i]: ms[i] / cnt[i] for i in names if cnt[i] > 0}
         rate = tr.rate if tr is not None else ARRIVAL_RATE
-        slots, inflight = step_accounting(handle, lib, one_step, args.steps, replay)
-        abytes = algorithmic_bytes(S, slots / B, inflight / B,
-                                   paired=True)  # duration "age", lost-FIN off: no plane
-        abytes[obs_name] = abytes.pop("observe_kernel")
-        abytes[dyn] = abytes.pop("dynamics_kernel")
-        abytes[fused] = abytes.pop("fused_step_kernel")
-        per_kernel = {}
-        for k in avg:
-            ab_k = abytes[k] * B
-            ach = ab_k / (avg[k] * 1e-3) / 1e9
-            per_kernel[k] = {"avg_launch_ms": avg[k], "algorithmic_bytes_per_launch": ab_k,
-                             "achieved_GBps": ach, "frac": ach / HBM_PEAK_GBS}
-        sigs = {names[c]: sig for c, sig in ran.items() if c in names}
-        for k in per_kernel:
-            per_kernel[k]["signature"] = sigs.get(k)
-        dom = max(avg, key=avg.get)
-        ab = abytes[dom] * B
-        achieved = ab / (avg[dom] * 1e-3) / 1e9
-        valu = valu_roofline(B, S, avg, sigs, slots / B)
-        traffic, traffic_note, traffic_workload = None, None, None
-        tfile = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tfile):
-            t = json.load(open(tfile))
-            held = t.get("bytes_per_launch", {})
-            traffic_workload = t.get("workload")
-            if t.get("batch") != B or t.get("servers") != S:
-                traffic_note = f"profiles/pmc_traffic.json is for {t.get('batch')} x {t.get('servers')}"
-            elif sigs.get(dom) not in held:
-                traffic_note = (f"profiles/pmc_traffic.json has no counters for {sigs.get(dom)!r} "
-                                f"(it holds {sorted(held)})")
-            else:
-                traffic_note = phase_mismatch(traffic_workload, slots / B, "pmc_traffic.json")
-                if traffic_note is None:
-                    traffic = held[sigs[dom]]
         out = {
             "metric": METRIC, "value": value, "unit": "env-steps/s",
             "n_gpus": dist.get_world_size() if world > 1 else 1,
@@ -760,27 +866,13 @@ def main():
                        "autoreset_mode": args.autoreset_mode if args.workload == "rollout"
                        else "same_step",
                        "parallelism": f"env-shard x{world}", "dyn_mapping": args.dyn_mapping},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": "profiles/pmc_traffic.json"
-                         if traffic is not None else None, "stale_reason": traffic_note,
-                         "traffic_workload": traffic_workload,
-                         "signature": sigs.get(dom), "algorithmic_bytes_per_launch": ab,
-                         "avg_launch_ms": avg[dom],
-                         "kernel_avg_ms": avg, "kernels": per_kernel, "valu": valu,
-                         # the two simulator kernels take about equal time: `kernel` is the longer
-                         # one this run; the dynamics kernel moves few bytes by construction (an
-                         # event loop, latency-bound: see `valu`), observe is the HBM-heavy one
-                         "hbm_heavy_kernel": (max(per_kernel, key=lambda k: per_kernel[k]
-                                                  ["algorithmic_bytes_per_launch"])
-                                              if per_kernel else None),
-                         "accounting": {"reservoir_slots_written_per_env_step": slots / B,
-                                        "flows_in_flight_per_env": inflight / B,
-                                        "basis": "lbsim_step_stats after each step of an exact "
-                                                 "replay of the timed steps" if replay else
-                                                 "lbsim_step_stats over as many further steps"}},
         }
+        if args.full:
+            out["roofline"] = roofline_leg(handle, lib, one_step, args.steps, replay, B, S, avg,
+                                           names, ran, dyn, obs_name, fused)
         out["prewarm"] = prewarm
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if args.workload != "rollout":
             out["config"]["workload"] = {
                 "sac-gru": f"problem-04 SAC-GRU actor (GRU {S * 11}->128, fc 128->256, heads "
@@ -799,20 +891,22 @@ def main():
                 fl = policy_flops(args.workload, S) * B
                 tf = fl / (pms * 1e-3) / 1e12
                 name = {"sac-gru": "sac_actor_kernel", "qmix": "qmix_policy_kernel"}[args.workload]
-                out["roofline"]["kernels"][name] = {
-                    "bound": "mfma", "avg_launch_ms": pms, "flops_per_launch": fl,
-                    "achieved_TFLOPs": tf, "peak_TFLOPs": MFMA_F32_PEAK_TFLOPS,
-                    "frac": tf / MFMA_F32_PEAK_TFLOPS}
+                if args.full:
+                    out["roofline"]["kernels"][name] = {
+                        "bound": "mfma", "avg_launch_ms": pms, "flops_per_launch": fl,
+                        "achieved_TFLOPs": tf, "peak_TFLOPs": MFMA_F32_PEAK_TFLOPS,
+                        "frac": tf / MFMA_F32_PEAK_TFLOPS}
                 # host + torch work between the launches (<= 10 us)
                 out["policy_glue_ms_per_step"] = out["policy_ms_per_step"] - pms
         if graph_res is not None:
             out["graph"] = graph_res
-        if world == 1 and args.workload == "rollout" and args.late_episode:
+        legs = args.full and world == 1 and args.workload == "rollout"
+        if legs and args.late_episode:
             out["late_episode"] = late_episode(args, env, handle, lib, one_step, rate, B, S,
                                                args.warmup + args.steps)
-        if world == 1 and args.workload == "rollout" and args.async_groups > 1:
+        if legs and args.async_groups > 1:
             out["async_groups"] = async_groups(args, dev, shard, B, S, common, args.async_groups)
-        if world == 1 and not args.no_cpu_baseline and args.workload == "rollout":
+        if legs and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     env.close()

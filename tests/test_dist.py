@@ -147,11 +147,11 @@ def test_bench_torchrun_rccl_world1():
 
 @pytest.mark.gpu
 def test_bench_graph_leg_runs_in_a_child_process():
-    """The graph leg runs in a child process (bench.graph_leg_child): the headline line carries
-    its result, marked as a child's, and the headline process never captures a graph."""
+    """The graph leg of a --full run is a child process (bench.graph_leg_child): the headline line
+    carries its result, marked as a child's, and the headline process never captures a graph."""
     import json
     root = os.path.dirname(HERE)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "5",
                         "--warmup", "2", "--batch", "2048", "--no-cpu-baseline", "--prewarm-ms", "0"],
                        cwd=root, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]

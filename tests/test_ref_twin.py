@@ -11,41 +11,46 @@ oracle -- test infrastructure checking test infrastructure.
   float32 summation-order tolerance; p90 differs by design -- the C twin takes the nearest index
   sorted[(int)(0.9f n)], the Python reference and the oracle numpy's linear interpolation -- so the
   twin's p90 is checked against that index of the sorted values.
+
+The twin's answers on these inputs are recorded in tests/golden/ref_twin.npz (gen_ref_twin.py), so
+the checks run wherever the suite runs; where the build compiled the twin it is also run again and
+must answer what is recorded.
 """
-import ctypes
 import os
+import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libref_reservoir.so")
-K = 128
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import gen_ref_twin as rec  # noqa: E402  (drives the twin; shared with the recorder)
+
+K = rec.K
 M64 = (1 << 64) - 1
 
 
 @pytest.fixture(scope="module")
+def gold(golden_dir):
+    """tests/golden/ref_twin.npz: the twin's answers on this module's inputs (gen_ref_twin.py)."""
+    return np.load(os.path.join(golden_dir, "ref_twin.npz"))
+
+
+@pytest.fixture(scope="module")
 def twin():
-    if not os.path.exists(LIB):
-        pytest.skip("oracle/_ref/libref_reservoir.so not built (needs /root/reference)")
-    lib = ctypes.CDLL(LIB)
-    lib.ref_reservoir_sizeof.restype = ctypes.c_size_t
-    lib.ref_reservoir_init.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
-    lib.ref_reservoir_add.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_uint64]
-    lib.ref_reservoir_add.restype = ctypes.c_int
-    lib.ref_reservoir_count.argtypes = [ctypes.c_void_p]
-    lib.ref_reservoir_count.restype = ctypes.c_uint64
-    lib.ref_reservoir_values.argtypes = [ctypes.c_void_p]
-    lib.ref_reservoir_values.restype = ctypes.POINTER(ctypes.c_float)
-    lib.ref_reservoir_stats.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_uint64,
-                                        ctypes.c_void_p]
-    return lib
+    """The twin itself where the build compiled it (the reference tree was present), else None:
+    the tests then check the recorded answers alone."""
+    return rec.load_twin() if os.path.exists(rec.LIB) else None
 
 
-def new_reservoir(lib, seed):
-    buf = ctypes.create_string_buffer(lib.ref_reservoir_sizeof())
-    lib.ref_reservoir_init(buf, seed)
-    return buf
+def twin_answers(twin, recorded, run):
+    """The twin's answers for one case: recorded ones, and where the twin is built also what it
+    answers now, which must be what is recorded."""
+    if twin is not None:
+        live = run(twin)
+        for a, b in zip(live, recorded):
+            np.testing.assert_array_equal(a, b)
+    return recorded
 
 
 def xorshift_state(seed):  # reservoir.h:55-74 reservoir_init
@@ -71,41 +76,38 @@ def algorithm_r_slot(count, draw):
 
 
 @pytest.mark.parametrize("seed", [0, 1, 20260109])
-def test_algorithm_r_rule_matches_the_c_twin(twin, seed):
-    r = new_reservoir(twin, seed)
+def test_algorithm_r_rule_matches_the_c_twin(twin, gold, seed):
+    vals = gold[f"algr_vals_{seed}"]
+    t_accepted, t_count, t_final = twin_answers(
+        twin, [gold[f"algr_accepted_{seed}"], gold[f"algr_count_{seed}"],
+               gold[f"algr_final_{seed}"]], lambda lib: rec.run_algr(lib, seed, vals))
+    assert len(vals) == 3000
     st = xorshift_state(seed)
     mine = np.zeros(K, np.float32)
-    rng = np.random.default_rng(seed)
-    vals = rng.uniform(0.0, 100.0, 3000).astype(np.float32)
     stored = 0
     for i, v in enumerate(vals):
         draw = xorshift128plus(st) % (i + 1) if i >= K else 0  # random_range(count + 1)
         slot = algorithm_r_slot(i, draw)
-        accepted = twin.ref_reservoir_add(r, float(v), i)
-        assert bool(accepted) == (slot >= 0), f"add {i}"
+        assert bool(t_accepted[i]) == (slot >= 0), f"add {i}"
         if slot >= 0:
             mine[slot] = v
             stored += 1
-        assert twin.ref_reservoir_count(r) == i + 1
-    got = np.ctypeslib.as_array(twin.ref_reservoir_values(r), shape=(K,))
-    np.testing.assert_array_equal(got, mine)
+        assert t_count[i] == i + 1
+    np.testing.assert_array_equal(t_final, mine)
     assert K < stored < len(vals)
 
 
-def test_algorithm_r_inclusion_probability_twin_and_oracle(twin, oracle_mod):
+def test_algorithm_r_inclusion_probability_twin_and_oracle(twin, gold, oracle_mod):
     """Each of N items ends in the reservoir with probability K/N under both RNGs (the twin's
     xorshift128+ and the oracle's Philox Algorithm R draw, oracle_algr_slot)."""
-    N, trials = 512, 300
+    N, trials = rec.INCL_N, rec.INCL_TRIALS
+    assert (N, trials) == (512, 300)
     lib = oracle_mod.load()
     key = np.array([20260109, 0], np.uint32)
-    hits_t = np.zeros(N)
+    (hits_t,) = twin_answers(twin, [gold["incl_hits"]], lambda t: [rec.run_inclusion(t)])
+    assert hits_t.shape == (N,) and hits_t.sum() == trials * K
     hits_o = np.zeros(N)
     for t in range(trials):
-        r = new_reservoir(twin, 1000 + t)
-        for i in range(N):
-            twin.ref_reservoir_add(r, float(i), i)
-        vals = np.ctypeslib.as_array(twin.ref_reservoir_values(r), shape=(K,)).astype(int)
-        hits_t[vals] += 1
         res = np.arange(K)
         for c in range(K, N):
             s = lib.oracle_algr_slot(c, t, 1, 0, oracle_mod.ptr(key))
@@ -119,32 +121,15 @@ def test_algorithm_r_inclusion_probability_twin_and_oracle(twin, oracle_mod):
         assert abs(z.mean()) < 0.2 and z.std() < 1.3, (z.mean(), z.std())
 
 
-def _stat_cases(rng):
-    cases = []
-    for n in (1, 5, 17, 64, 100, 128):
-        for kind in range(3):
-            if kind == 0:
-                v = (rng.exponential(8e3, n).astype(np.int64) + 1).astype(np.float32) * np.float32(1e-6)
-            elif kind == 1:
-                v = rng.uniform(1.0, 50.0, n).astype(np.float32)
-            else:
-                v = rng.choice(np.float32([0.5, 1.0, 2.0, 4.0]), n)
-            age_ms = rng.integers(0, 20000, n)
-            cases.append((v.astype(np.float32), age_ms))
-    return cases
-
-
-def test_statistics_c_twin_vs_oracle(twin, oracle_mod):
-    rng = np.random.default_rng(7)
-    now_ms = 50_000
-    for v, age_ms in _stat_cases(rng):
+def test_statistics_c_twin_vs_oracle(twin, gold, oracle_mod):
+    now_ms = rec.STAT_NOW_MS
+    assert int(gold["stat_cases"]) == 18
+    for case in range(18):
+        v, age_ms = gold[f"stat_v_{case}"], gold[f"stat_age_{case}"]
         n = len(v)
-        r = new_reservoir(twin, 3)
         ts_ms = (now_ms - age_ms).astype(np.uint32)
-        for i in range(n):
-            twin.ref_reservoir_add(r, float(v[i]), int(ts_ms[i]) * 1000)  # us timestamps
-        c_out = np.zeros(5, np.float32)
-        twin.ref_reservoir_stats(r, 0.9, now_ms * 1000, c_out.ctypes.data)
+        (c_out,) = twin_answers(twin, [gold[f"stat_out_{case}"]],
+                                lambda lib: [rec.run_stats(lib, v, age_ms)])
         vv = np.zeros(K, np.float32)
         vv[:n] = v
         tt = np.zeros(K, np.uint32)

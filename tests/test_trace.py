@@ -1,14 +1,13 @@
 """Trace arrival source: CSV/npz ingestion and the oracle's replay
 rule (row (gid * 7919 + (episode - 1) * 1000003 + k) mod R for the k-th arrival)."""
+import json
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from marllb_amd import trace
-
-REF_CSV = "/root/reference/data/trace/poisson_for_loop/rate_500.csv"
-
 
 def test_builtin_trace_shape_and_rate():
     t = trace.builtin()
@@ -18,11 +17,18 @@ def test_builtin_trace_shape_and_rate():
     assert t.gap_us[0] == round(int(t.gap_us[1:].sum()) / (t.rows - 1))  # wrap gap = mean gap
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CSV), reason="reference tree not present")
-def test_builtin_npz_equals_reference_csv():
-    a, b = trace.builtin(), trace.load_csv(REF_CSV)
-    np.testing.assert_array_equal(a.gap_us, b.gap_us)
-    np.testing.assert_array_equal(a.work, b.work)
+def test_builtin_npz_equals_reference_csv(golden_dir):
+    """Every gap and work value of the built-in npz equals what load_csv made of the reference's
+    own CSV: tests/golden/trace_rate_500.json records the two arrays' SHA-256 (gen_trace.py; the
+    CSV itself is too large to keep here)."""
+    sys.path.insert(0, golden_dir)
+    import gen_trace
+    want = json.load(open(os.path.join(golden_dir, "trace_rate_500.json")))
+    got = gen_trace.record(trace.builtin())
+    assert got["rows"] == want["rows"] == 77965
+    assert got["gap_us_sha256"] == want["gap_us_sha256"]
+    assert got["work_sha256"] == want["work_sha256"]
+    assert got["rate"] == want["rate"]
 
 
 def test_from_times_rules(tmp_path):

@@ -25,7 +25,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for c in "${CFG[@]}"; do
     for n in "$@"; do
       echo "{\"variant\": \"$n\", \"round\": $r, \"args\": \"$c\"}" >> $O/ab.jsonl
-      LBSIM_LIBRARY=$(lib $n) timeout -k 10 240 python bench.py --no-cpu-baseline --steps ${STEPS:-30} --warmup 5 $c >> $O/ab.jsonl 2> $O/err_$n.log || exit 12
+      LBSIM_LIBRARY=$(lib $n) timeout -k 10 240 python bench.py --full --no-cpu-baseline --steps ${STEPS:-30} --warmup 5 $c >> $O/ab.jsonl 2> $O/err_$n.log || exit 12
     done
   done
 done

@@ -19,6 +19,6 @@ for rep in 1 2; do
     lib=""
     [ "$name" != "cur" ] && lib="LBSIM_LIBRARY=$R/marllb_amd/exp/liblbsim_$name.so"
     echo "== $v rep $rep" >> $O/ab.jsonl
-    env $lib $envs timeout -k 10 240 python bench.py --no-cpu-baseline --no-graph --steps 50 --warmup 10 "$@" >> $O/ab.jsonl 2>> $O/ab.err || exit 20
+    env $lib $envs timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-graph --steps 50 --warmup 10 "$@" >> $O/ab.jsonl 2>> $O/ab.err || exit 20
   done
 done

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 # the driver's bench command (--steps 20 --warmup 5, pre-warm on) without the graph leg and the CPU
 # baseline, which run after the timed region; tools/pmc_traffic.py / pmc_valu.py --steps 20
 # --warmup 5 keep the timed launches (and their exact accounting replay) only
-B="$R/bench.py --no-cpu-baseline --no-graph --steps 20 --warmup 5 $@"
+B="$R/bench.py --full --no-cpu-baseline --no-graph --steps 20 --warmup 5 $@"
 P="timeout -s KILL 240 rocprofv3"
 $P --pmc FETCH_SIZE -d $O/fetch -o run --output-format csv -- python3 $B > $O/fetch.log 2>&1 &&
 $P --pmc WRITE_SIZE -d $O/write -o run --output-format csv -- python3 $B > $O/write.log 2>&1 &&

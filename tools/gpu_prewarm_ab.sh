@@ -11,6 +11,6 @@ cd $R
 for rep in 1 2; do
   for a in "--steps 20 --warmup 5 --prewarm-ms 0" "--steps 20 --warmup 5 --prewarm-ms 200" "--steps 50 --warmup 10 --prewarm-ms 0" "--steps 50 --warmup 10 --prewarm-ms 200"; do
     echo "== $a rep $rep" >> $O/prewarm.jsonl
-    timeout -k 10 240 python bench.py --gpus 1 --no-cpu-baseline --no-graph $a >> $O/prewarm.jsonl 2>> $O/prewarm.err || exit 30
+    timeout -k 10 240 python bench.py --full --gpus 1 --no-cpu-baseline --no-graph $a >> $O/prewarm.jsonl 2>> $O/prewarm.err || exit 30
   done
 done

@@ -16,4 +16,4 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
 fi
 bash tools/gpu_lib_ab.sh $TAG/ab $VARS -- || exit 12
 bash tools/gpu_lib_ab.sh $TAG/modes ${MODES:-cur} -- --autoreset-mode next_step || exit 13
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench.err || exit 14
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench.err || exit 14

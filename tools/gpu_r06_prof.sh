@@ -12,9 +12,9 @@ mkdir -p $O
 cp $R/profiles/r03/ubench_valu.jsonl $O/
 cd /tmp && export TMPDIR=/tmp
 P="timeout -s KILL 240 rocprofv3"
-$P --kernel-trace --stats -d $O/trace_default -o run --output-format csv -- python3 $R/bench.py --no-graph --no-cpu-baseline > $O/trace_default.json 2> $O/trace_default.err || exit 20
-$P --kernel-trace --stats -d $O/trace_driver -o run --output-format csv -- python3 $R/bench.py --no-graph --no-cpu-baseline --steps 20 --warmup 5 > $O/trace_driver.json 2> $O/trace_driver.err || exit 21
-B="$R/bench.py --no-cpu-baseline --no-graph --steps 20 --warmup 5"
+$P --kernel-trace --stats -d $O/trace_default -o run --output-format csv -- python3 $R/bench.py --full --no-graph --no-cpu-baseline > $O/trace_default.json 2> $O/trace_default.err || exit 20
+$P --kernel-trace --stats -d $O/trace_driver -o run --output-format csv -- python3 $R/bench.py --full --no-graph --no-cpu-baseline --steps 20 --warmup 5 > $O/trace_driver.json 2> $O/trace_driver.err || exit 21
+B="$R/bench.py --full --no-cpu-baseline --no-graph --steps 20 --warmup 5"
 $P --pmc FETCH_SIZE -d $O/fetch -o run --output-format csv -- python3 $B > $O/fetch.log 2>&1 &&
 $P --pmc WRITE_SIZE -d $O/write -o run --output-format csv -- python3 $B > $O/write.log 2>&1 &&
 $P --pmc FETCH_SIZE -d $O/calf -o run --output-format csv -- python3 $R/tools/pmc_calib.py > $O/calf.log 2>&1 &&

@@ -14,6 +14,6 @@ for w in qmix sac-gru; do
 done
 for rep in 1 2; do
   for w in sac-gru qmix; do
-    timeout -k 10 300 python bench.py --no-cpu-baseline --no-graph --steps 50 --warmup 10 --workload $w >> $O/policy.jsonl 2>> $O/bench.err || exit 12
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-graph --steps 50 --warmup 10 --workload $w >> $O/policy.jsonl 2>> $O/bench.err || exit 12
   done
 done

@@ -15,6 +15,6 @@ for r in 1 2 3; do
       r02) cd $R/expl/r02; X="" ;;
       r03) cd $R; X=--no-graph ;;
     esac
-    timeout -k 10 240 python bench.py --no-cpu-baseline --steps 50 --warmup 10 $X >> $O/ab.jsonl 2>> $O/err.log || exit 12
+    timeout -k 10 240 python bench.py --full --no-cpu-baseline --steps 50 --warmup 10 $X >> $O/ab.jsonl 2>> $O/err.log || exit 12
   done
 done

@@ -11,6 +11,6 @@ cd $R
 : > $O/sweep.jsonl
 for S in 4 8; do
   for B in 4096 16384 65536 131072 262144 524288; do
-    timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --warmup 3 --batch $B --servers $S "$@" >> $O/sweep.jsonl 2>> $O/sweep_err.log || exit 31
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 --batch $B --servers $S "$@" >> $O/sweep.jsonl 2>> $O/sweep_err.log || exit 31
   done
 done

@@ -56,7 +56,7 @@ def is_step_kernel(k: str) -> bool:
 
 def timed_positions(n: int, steps: int, warmup: int):
     """Positions (in dispatch order) of the timed steps among the n step-mode dispatches of one
-    kernel signature in a `bench.py --no-graph` run: the measured env runs W warm-up + K timed
+    kernel signature in a `bench.py --full --no-graph` run: the measured env runs W warm-up + K timed
     steps, then the accounting replay (bench.step_accounting: a twin env from the same seeds)
     runs the same W + K steps bit for bit, so the run ends with [W | K | W | K]; a pre-warm's
     scratch env (its own episode phase) comes before and is excluded.  The counters are then those
