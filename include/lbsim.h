@@ -131,7 +131,7 @@ enum lbsim_dyn_kernel {
  * one-wave-per-env handles, fused_step_kernel for server-per-lane groups of <= 16 lanes (else
  * SPLIT); SPLIT: a dynamics launch and an observe launch.  AUTO: the one-launch step_wave_kernel
  * for one-wave-per-env handles with S <= 8 and at most 4 envs per SIMD (the single-env facade
- * and BASELINE configs[1]'s 4096 x 4 on 256 CUs; LBSIM_STEP_WAVE_MAX_B overrides the limit),
+ * and BASELINE configs[1]'s 4096 x 4 on 256 CUs),
  * else SPLIT (the server-per-lane fused form measured slower).  The environment
  * variable LBSIM_STEP_KERNEL=split|fused overrides AUTO. */
 enum lbsim_step_kernel { LBSIM_STEP_AUTO = 0, LBSIM_STEP_SPLIT = 1, LBSIM_STEP_FUSED = 2 };
@@ -469,8 +469,7 @@ int lbsim_vpp_features(const float* tv, const float* ts, int64_t res_per_ts, int
  * in ms (ms_out[4]) and the number of timed launches (count_out[4]).  lbsim_profile_end_ex
  * returns the first n_classes (<= LBSIM_PROFILE_CLASSES) classes, class 4 being the fused step
  * kernel.  Used by bench.py.  The events are created with hipEventDisableSystemFence (no cache
- * writeback / invalidate between the bracketed launches; LBSIM_PROFILE_FENCE=1 restores default
- * events): read the times only after synchronising the device, as lbsim_profile_end's callers do.
+ * writeback / invalidate between the bracketed launches): read the times only after synchronising the device, as lbsim_profile_end's callers do.
  */
 #define LBSIM_PROFILE_CLASSES 5
 /* (lbsim_profile_end reports the first 4 classes only: a handle whose steps are one launch --

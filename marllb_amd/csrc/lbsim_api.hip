@@ -450,22 +450,17 @@ int step_kernel_of(const lbsim_t* h) {
 }
 
 // The one-launch wave step (step_wave_kernel): one wave per env and S <= 8, FUSED asked for, or
-// AUTO on batches of at most 4 envs per SIMD (LBSIM_STEP_WAVE_MAX_B overrides), where one launch
-// instead of two pays: 2048 x 4 0.0711 -> 0.0620 ms per step, 4096 x 4 +2.5 %
-// (profiles/r03w/ab_step_wave_fused.txt).  S = 5-8 between 2 and 4 envs per SIMD: the wave
-// dynamics alone lose to the server-per-lane groups there (dyn_wave_ok), the one launch with both
-// chunks observed in it wins (profiles/r04s/).
+// AUTO on batches of at most 4 envs per SIMD, where one launch instead of two pays: 2048 x 4
+// 0.0711 -> 0.0620 ms per step, 4096 x 4 +2.5 % (profiles/r03w/ab_step_wave_fused.txt).  S = 5-8
+// between 2 and 4 envs per SIMD: the wave dynamics alone lose to the server-per-lane groups there
+// (dyn_wave_ok), the one launch with both chunks observed in it wins (profiles/r04s/).
 bool use_step_wave(const lbsim_t* h) {
-  static const int64_t max_b = [] {
-    const char* e = std::getenv("LBSIM_STEP_WAVE_MAX_B");
-    return e ? (int64_t)std::atoll(e) : (int64_t)-1;
-  }();
   const LaunchCtx L = ctx(h);
   // next-step auto-reset handles step in two launches (the dynamics' kModeStepNR instantiation)
   if (!dyn_wave_fits(L) || h->prm.next_reset) return false;
   const int k = step_kernel_of(h);
   if (k == LBSIM_STEP_FUSED) return dyn_wave_ok(L);
-  return k == LBSIM_STEP_AUTO && (int64_t)L.B <= (max_b >= 0 ? max_b : 4 * (int64_t)L.simds);
+  return k == LBSIM_STEP_AUTO && (int64_t)L.B <= 4 * (int64_t)L.simds;
 }
 
 // The fused step for this handle: its config (LBSIM_STEP_KERNEL=split|fused overrides AUTO) and
@@ -488,25 +483,19 @@ int launch_observe(lbsim_t* h, const ObsOutputs& o, const uint8_t* mask, int mod
   return launch_check(h, "observe_kernel");
 }
 
-// ---- one-kernel policy inference (lbsim_fused.h)
+// ---- one-kernel policy inference (lbsim_fused.h; the LDS layout and its sizing: lbsim_pol.hip)
 
-// LDS row stride of the fused kernels: >= need floats and = 4 (mod 64), so the 16 rows one
-// ds_read_b128 touches fall in distinct banks.
-int fused_ld(int need) { return ((need - 4 + 63) / 64) * 64 + 4; }
 int round16(int x) { return (x + 15) / 16 * 16; }
-constexpr size_t kFusedLdsMax = 160 * 1024;
 
 // Envs per workgroup = 16 MT.  QMIX's tile kernel: MT = 1 (8192 x 16 0.121 / 0.157 / 0.251 ms at
 // MT = 1 / 2 / 4, profiles/r01s3a).  The SAC actor: MT = 2 since round 6 -- with its staging one
 // HBM round trip (r06n), a 32-env tile halves the weight stream per env, and the weight stream is
 // what the staging waited behind: 187-188 -> 179.3-179.7 us at 65536 x 8, 0.53 -> 0.556 of the
 // f32 MFMA peak (profiles/r06q/; round 1, with the staging serialised, MT = 2 was the slower:
-// 0.231 vs 0.267 ms).  LBSIM_FUSED_MT = 1 | 2 | 4 forces it for both.
-int fused_mt(int64_t, int dflt = 1) {
-  static const int forced = [] {
-    const char* s = std::getenv("LBSIM_FUSED_MT");
-    return s ? std::atoi(s) : 0;
-  }();
+// 0.231 vs 0.267 ms).  LBSIM_FUSED_MT = 1 | 2 | 4 forces it for both.  The launchers halve it
+// until the tile's LDS fits.
+int fused_mt(int dflt) {
+  static const int forced = env_int("LBSIM_FUSED_MT", 0);
   return (forced == 1 || forced == 2 || forced == 4) ? forced : dflt;
 }
 
@@ -882,7 +871,6 @@ int lbsim_sac_actor_step(const lbsim_sac_actor_t* n, const float* state, float* 
   a.B = B;
   a.I = n->state_dim;
   a.kxp = round16(n->state_dim);
-  a.ld = fused_ld(std::max(a.kxp + 128, 256));
   a.A = n->action_dim;
   a.lo = n->log_std_min;
   a.hi = n->log_std_max;
@@ -893,18 +881,7 @@ int lbsim_sac_actor_step(const lbsim_sac_actor_t* n, const float* state, float* 
   a.key1 = (uint32_t)(seed >> 32);
   a.step = step;
   a.step_dev = n->step_dev;
-  int mt = fused_mt(B, 2);
-  // the [R][ld] tile + split-K scratch of the heads ([4][nt][R][16], nt = ceil(2A / 16)): at A = 8
-  // 20.6 KB per 16-env tile, 7 tiles per CU
-  const int nt_heads = (2 * a.A + 15) / 16;
-  // (the 32-env tile's heads keep two partials per row, not four: LBSIM_SAC_SPLIT_M, lbsim_fused.h)
-  auto lds_of = [&](int m) {
-    return (size_t)16 * m * (a.ld + (m == 2 && LBSIM_SAC_SPLIT_M ? 32 : 64) * nt_heads) * 4;
-  };
-  while (mt > 1 && lds_of(mt) > kFusedLdsMax) mt >>= 1;
-  const size_t lds = lds_of(mt);
-  const hipStream_t s = (hipStream_t)stream;
-  return launch_sac_actor(a, B, mt, lds, s);
+  return launch_sac_actor(a, B, fused_mt(2), (hipStream_t)stream);
 }
 
 int lbsim_qmix_policy_step(const lbsim_qmix_policy_t* n, const float* obs, float* hidden,
@@ -962,7 +939,6 @@ int lbsim_qmix_policy_step(const lbsim_qmix_policy_t* n, const float* obs, float
   a.kxp = round16(n->obs_dim);
   a.Ds = n->state_dim;
   a.ksp = round16(n->state_dim);
-  a.ld = fused_ld(std::max({a.kxp + 64, 128, a.ksp, 3 * he + E}));
   a.n_act = n->n_actions;
   a.k = n->servers_per_agent;
   a.he = he;
@@ -972,13 +948,6 @@ int lbsim_qmix_policy_step(const lbsim_qmix_policy_t* n, const float* obs, float
   a.key1 = (uint32_t)(seed >> 32);
   a.step = step;
   a.step_dev = n->step_dev;
-  auto lds_of = [&](int mt) {
-    const size_t R = 16 * (size_t)mt;
-    return (R * a.ld + (size_t)A * R * 16 + R * A + 64 * R) * 4;  // + split-K scratch
-  };
-  int mt = fused_mt(B);
-  while (mt > 1 && lds_of(mt) > kFusedLdsMax) mt >>= 1;
-  const hipStream_t s = (hipStream_t)stream;
   // LBSIM_QMIX_KERNEL = tile | wave | pair (default: pair when A = 4, else wave)
   static const int form = [] {
     const char* e = std::getenv("LBSIM_QMIX_KERNEL");
@@ -986,23 +955,7 @@ int lbsim_qmix_policy_step(const lbsim_qmix_policy_t* n, const float* obs, float
     if (e != nullptr && std::strcmp(e, "wave") == 0) return 1;
     return 2;
   }();
-  if (mt == 1 && form != 0) {  // one or two waves per agent, 16 envs per workgroup
-    a.lda = fused_ld(std::max(a.kxp + 64, 128));
-    if (form == 2 && A == 4) {  // two waves per agent: 8-wave workgroups
-      // + the mixer's state rows, staged at the start when they fit (a.sld = 0: staged by the
-      // mixer, as the other forms)
-      const size_t base = ((size_t)4 * 16 * a.lda + 2 * (size_t)A * 16 * 16 + 16 * (size_t)A) * 4;
-      a.sld = fused_ld(a.ksp);
-      if (base + (size_t)16 * a.sld * 4 > kFusedLdsMax) a.sld = 0;
-      const size_t lds = base + (size_t)16 * a.sld * 4;
-      if (a.ld > 4 * a.lda || lds > kFusedLdsMax) return LBSIM_ENOTSUP;
-      return launch_qmix_policy(a, B, 2, 1, lds, s);
-    }
-    const size_t lds = ((size_t)4 * 16 * a.lda + (size_t)A * 16 * 16 + 16 * (size_t)A) * 4;
-    if (a.ld > 4 * a.lda || lds > kFusedLdsMax) return LBSIM_ENOTSUP;
-    return launch_qmix_policy(a, B, 1, 1, lds, s);
-  }
-  return launch_qmix_policy(a, B, 0, mt, lds_of(mt), s);
+  return launch_qmix_policy(a, B, form, fused_mt(1), (hipStream_t)stream);
 }
 
 int lbsim_alias_tables(const float* weights, int64_t n, int S, float* odd_out, int32_t* alias_out,
@@ -1082,15 +1035,10 @@ int lbsim_profile_begin(lbsim_t* h, int max_launches) {
   // Timing-only events: no system-scope fence when they are recorded.  A default event's record
   // writes back and invalidates the caches between the launches it brackets, which costs the
   // timed step itself (the caller synchronises the device before reading the times, so nothing
-  // needs the fence).  LBSIM_PROFILE_FENCE=1 keeps the default events (A/B).
-  static const unsigned flags = [] {
-    const char* e = std::getenv("LBSIM_PROFILE_FENCE");
-    return (e != nullptr && std::strcmp(e, "1") == 0) ? (unsigned)hipEventDefault
-                                                       : (unsigned)hipEventDisableSystemFence;
-  }();
+  // needs the fence).
   while (p.ev.size() < need) {
     hipEvent_t e;
-    if (hipEventCreateWithFlags(&e, flags) != hipSuccess)
+    if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess)
       return fail(h, LBSIM_EDEVICE, "hipEventCreateWithFlags failed");
     p.ev.push_back(e);
   }

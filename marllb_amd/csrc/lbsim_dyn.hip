@@ -33,10 +33,7 @@ template <int G, int POLICY>
 void launch_dyn_group(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
                       const uint8_t* mask, hipStream_t stream) {
   // envs per wave: 64 / G; LBSIM_DYN_EPW (1 .. 64 / G) runs fewer per wave, more waves
-  static const int forced_epw = [] {
-    const char* e = std::getenv("LBSIM_DYN_EPW");
-    return e ? std::atoi(e) : 0;
-  }();
+  static const int forced_epw = env_int("LBSIM_DYN_EPW", 0);
   const int epw = (forced_epw >= 1 && forced_epw <= 64 / G) ? forced_epw : 64 / G;
   SimParams prm = L.prm;
   prm.dyn_epw = epw;

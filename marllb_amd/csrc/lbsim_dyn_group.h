@@ -31,13 +31,6 @@
 namespace lbk {
 
 constexpr int kGroupWL = 8;  // LDS queue window per server: 64 lanes x 8 x 8 B = 4 KiB per wave
-// kModeStepNR: 1 = the Philox round keys formed inside the draw-ahead block (group_event_loop
-// KEYS: 120 VGPRs, no spills); 0 = hoisted as in the plain step (126 VGPRs at the 4-wave cap, 4
-// spilled): 152.1-152.8 -> 150.6 us at 65536 x 4 (profiles/r06i/) -- the plain kernel shed the
-// full handles' code, so the hoisted keys fit the budget again
-#ifndef LBSIM_DYN_NR_KEYS
-#define LBSIM_DYN_NR_KEYS 0
-#endif
 
 // Reductions over the aligned G-lane group (G <= 16: one DPP row).  Lanes read only within their
 // group, so groups that left the event loop (inactive lanes) are never read.  mov_dpp with
@@ -270,14 +263,16 @@ __device__ __forceinline__ GroupConst group_const(const SimParams& p, uint32_t b
 }
 
 // The event loop of sim_step_group (section 2).  FAST (wave-uniform): every SED score finite, so no
-// NaN fallback division and no NaN ballot.  KEYS: the Philox round keys are formed inside the
-// draw-ahead block instead of being hoisted into 20 loop-long VGPRs (LBSIM_DYN_NR_KEYS for
-// kModeStepNR; the plain step hoists them: 4 us faster at 65536 x 4, profiles/r06c/).
+// NaN fallback division and no NaN ballot.  The Philox round keys of the draw-ahead block are
+// hoisted into 20 loop-long VGPRs in every mode: forming them inside the block measured 4 us
+// slower at 65536 x 4 in the plain step (profiles/r06c/), and in kModeStepNR (120 VGPRs and no
+// spills, against 126 at the 4-wave cap with 4 spilled) 152.1-152.8 against 150.6 us
+// (profiles/r06i/) -- the plain kernel shed the full handles' code, so the hoisted keys fit.
 // FULL: the handle's features beyond the plain simulator -- n_flow_on_mode VPP's lost-flow counts,
 // a duration plane (duration_mode SERVICE), lost-FIN deferral (split reservoirs), reservoir_mode
 // VPP -- compiled only into dynamics_group_full_kernel, so none of their registers weigh on the
 // plain kernel (126 VGPRs, 4 waves per SIMD; with them inlined it took 164).
-template <int G, int POLICY, bool TRACE, bool FAST, bool KEYS = false, bool FULL = false>
+template <int G, int POLICY, bool TRACE, bool FAST, bool FULL = false>
 __device__ __forceinline__ void group_event_loop(const DevState& st, const SimParams& p,
                                                  LaneState<1>& E, SrvLane& V, int s, int gbase,
                                                  int n_alias, const GroupConst& gc, int2* win,
@@ -311,8 +306,7 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
       cbase = E.arr_idx + 1u;
       const uint32_t k = cbase + (uint32_t)s;
       uint32_t rk0[10], rk1[10];
-      uint32_t k0 = gc.k0, k1 = gc.k1;
-      if constexpr (KEYS) asm volatile("" : "+v"(k0), "+v"(k1));  // opaque: not hoisted
+      const uint32_t k0 = gc.k0, k1 = gc.k1;
 #pragma unroll
       for (int r = 0; r < 10; ++r) {
         rk0[r] = k0 + (uint32_t)r * 0x9E3779B9u;
@@ -491,7 +485,7 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
   }
 }
 
-template <int G, int POLICY, bool TRACE, bool KEYS = false, bool FULL = false>
+template <int G, int POLICY, bool TRACE, bool FULL = false>
 __device__ __forceinline__ void sim_step_group(const DevState& st, const SimParams& p,
                                                LaneState<1>& E, SrvLane& V, uint32_t b, int s,
                                                int gbase, float w_own, const float (&wall)[G],
@@ -615,16 +609,16 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
   const bool finite = lsq || alias || !V.act ||
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
-    group_event_loop<G, POLICY, TRACE, false, KEYS, true>(st, p, E, V, s, gbase, n_alias, gc, win,
-                                                          atab, acache, my_res, my_ring);
+    group_event_loop<G, POLICY, TRACE, false, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
+                                                    acache, my_res, my_ring);
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
   } else if (__all(finite)) {
-    group_event_loop<G, POLICY, TRACE, true, KEYS>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                                   acache, my_res, my_ring);
+    group_event_loop<G, POLICY, TRACE, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
+                                             acache, my_res, my_ring);
   } else {
-    group_event_loop<G, POLICY, TRACE, false, KEYS>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                                    acache, my_res, my_ring);
+    group_event_loop<G, POLICY, TRACE, false>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
+                                              acache, my_res, my_ring);
   }
 
   // ---- rebase to the next step's start (this lane's server)
@@ -827,13 +821,13 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
   };
   if constexpr (MODE == kModeStep) {
     load_in();
-    sim_step_group<G, POLICY, TRACE, false, FULL>(st, p, E, V, b, s, gbase, w_own, wall, win, atab,
-                                                  acache);
+    sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w_own, wall, win, atab,
+                                           acache);
   } else if constexpr (MODE == kModeReset) {
     reset_in();
     for (int k = 0; k < p.warmup_steps; ++k)
-      sim_step_group<G, POLICY, TRACE, false, FULL>(st, p, E, V, b, s, gbase, 1.0f, wall, win,
-                                                    atab, acache);
+      sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, 1.0f, wall, win, atab,
+                                             acache);
     reset_out(0);
   } else {
     // kModeStepNR (next-step auto-reset): an env whose last step returned done resets in place of
@@ -848,8 +842,8 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     const int nsteps = rs ? p.warmup_steps : 1;
     const float w = rs ? 1.0f : w_own;
     for (int k = 0; k < nsteps; ++k)
-      sim_step_group<G, POLICY, TRACE, LBSIM_DYN_NR_KEYS != 0, FULL>(st, p, E, V, b, s, gbase, w,
-                                                                     wall, win, atab, acache);
+      sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w, wall, win, atab,
+                                             acache);
     if (rs) reset_out(-1);
   }
 

@@ -35,15 +35,6 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f4 splat4(float v) { return f4{v, v, v, v}; }
 
-// Timing diagnostic only (wrong results): LBSIM_EXP_L1W=1 makes every k-block past the first two
-// re-read one of the tile's first two weight blocks: fewer distinct weight bytes, the same stream
-// of weight requests (a CU's ~24 waves' blocks still overflow its L1; profiles/r06k/).
-#if LBSIM_EXP_L1W
-#define LBSIM_EXP_WBLK(n) ((n) & 1)
-#else
-#define LBSIM_EXP_WBLK(n) (n)
-#endif
-
 // Timing diagnostic only (LBSIM_EXP_PHASES=1, pol.o of an A/B build): lane 0 of wave 0 of every
 // gridDim / 64-th workgroup records the 100 MHz clock at the kernel's phase boundaries into
 // lbsim_exp_ts[sample][phase] (read by lbsim_exp_phase_read, tools/policy_phases.py).
@@ -77,7 +68,7 @@ __device__ __forceinline__ void mma_tile(f4 (&acc)[MT], const float* lds, int ld
   for (int kb = 0; kb < nkb; ++kb) {
     const int n2 = kb + 2 < nkb ? kb + 2 : nkb - 1;
     const int n1 = kb + 1 < nkb ? kb + 1 : nkb - 1;
-    const f4 b2 = wp[LBSIM_EXP_WBLK(n2) * 64 + lane];
+    const f4 b2 = wp[n2 * 64 + lane];
     f4 an[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) an[m] = *(const f4*)(arow + m * 16 * ld + n1 * 16);
@@ -137,7 +128,7 @@ __device__ __forceinline__ void mma_multi(f4 (&acc)[NB][MT], const float* lds, i
     const int n1 = kb + 1 < nkb ? kb + 1 : nkb - 1;
     f4 b2[NB];
 #pragma unroll
-    for (int j = 0; j < NB; ++j) b2[j] = wp[j][LBSIM_EXP_WBLK(n2) * 64 + lane];
+    for (int j = 0; j < NB; ++j) b2[j] = wp[j][n2 * 64 + lane];
     f4 an[MT];
 #pragma unroll
     for (int m = 0; m < MT; ++m) an[m] = *(const f4*)(arow + m * 16 * ld + n1 * 16);
@@ -220,7 +211,7 @@ __device__ __forceinline__ void splitk_out(const float* lds, int ld, const float
 // splitk_out for a 32-row tile (MT = 2): wave w runs M-tile w >> 1 over the k-blocks of half
 // (w & 1), so the scratch holds two partials per row ([2][nt][32][16]) instead of four -- the
 // SAC tile's LDS is then 37.4 KB, four workgroups per CU where the four-partial scratch (41.5 KB)
-// fit three (LBSIM_SAC_SPLIT_M).  Contains a barrier; the caller barriers again before reading dst.
+// fit three.  Contains a barrier; the caller barriers again before reading dst.
 __device__ __forceinline__ void splitk_out_m2(const float* lds, int ld, const float* __restrict__ w,
                                               const float* __restrict__ bias, int nkb, int nt,
                                               float* scratch, float* dst, int dld, int ncols,
@@ -402,11 +393,6 @@ struct SacActorArgs {
 template <int R, int H>
 __device__ __forceinline__ void stage_sac_rows(float* lds, const SacActorArgs& p, int64_t row0) {
   const int t = threadIdx.x, kxp = p.kxp, ld = p.ld;
-#if LBSIM_EXP_NOSTAGE  // timing diagnostic (wrong results): no HBM reads in the staging
-  for (int c = t; c < kxp + H; c += blockDim.x)
-    for (int r = 0; r < R; ++r) lds[r * ld + c] = 0.01f * (float)c;
-  return;
-#endif
   for (int c = t; c < kxp + H; c += blockDim.x) {
     const bool st = c < kxp;
     const bool col_ok = !st || c < p.I;
@@ -435,17 +421,26 @@ __device__ __forceinline__ void stage_sac_rows(float* lds, const SacActorArgs& p
   }
 }
 
-#ifndef LBSIM_SAC_WPE
-#define LBSIM_SAC_WPE 1
-#endif
-// 1: the 32-env SAC tile's heads split their K over 2 waves per M-tile (splitk_out_m2), the LDS
-// scratch halved (lbsim_api.hip sac_lds_bytes must agree)
-#ifndef LBSIM_SAC_SPLIT_M
-#define LBSIM_SAC_SPLIT_M 1
-#endif
+// LDS row stride of the fused kernels: >= need floats and = 4 (mod 64), so the 16 rows one
+// ds_read_b128 touches fall in distinct banks.
+inline int fused_ld(int need) { return ((need - 4 + 63) / 64) * 64 + 4; }
+// What a fused kernel's workgroup may ask for of a CU's 160 KB LDS.
+constexpr size_t kFusedLdsMax = 160 * 1024;
+
+// Waves per SIMD sac_actor_kernel is built for.
+constexpr int kSacWavesPerSimd = 1;
+
+// LDS bytes of sac_actor_kernel<MT>: the [R][ld] tile + the heads' split-K scratch ([4][nt][R][16],
+// nt = ceil(2A / 16); the 32-env tile's heads split their K over 2 waves per M-tile,
+// splitk_out_m2, and keep two partials per row, not four).  At A = 8 20.6 KB per 16-env tile, 7
+// tiles per CU.
+inline size_t sac_actor_lds_bytes(int mt, int ld, int A) {
+  const int nt_heads = (2 * A + 15) / 16;
+  return (size_t)16 * mt * (ld + (mt == 2 ? 32 : 64) * nt_heads) * 4;
+}
 
 template <int MT, int H, int F>
-__global__ void __launch_bounds__(256, LBSIM_SAC_WPE) sac_actor_kernel(SacActorArgs p) {
+__global__ void __launch_bounds__(256, kSacWavesPerSimd) sac_actor_kernel(SacActorArgs p) {
   const uint32_t step = p.step_dev != nullptr ? *p.step_dev : p.step;
   extern __shared__ float lds[];
   constexpr int R = 16 * MT;
@@ -453,12 +448,7 @@ __global__ void __launch_bounds__(256, LBSIM_SAC_WPE) sac_actor_kernel(SacActorA
   const int64_t row0 = (int64_t)blockIdx.x * R;
   const int ld = p.ld, kxp = p.kxp;
   LB_PHASE(0);
-#if LBSIM_SAC_OLD_STAGE
-  stage_rows(lds, ld, 0, p.state, p.I, p.I, kxp, R, row0, p.B, nullptr);
-  stage_rows(lds, ld, kxp, p.hidden, H, H, H, R, row0, p.B, p.reset);
-#else
   stage_sac_rows<R, H>(lds, p, row0);
-#endif
   LB_PHASE(1);
   __syncthreads();
   LB_PHASE(2);
@@ -483,7 +473,7 @@ __global__ void __launch_bounds__(256, LBSIM_SAC_WPE) sac_actor_kernel(SacActorA
   LB_PHASE(6);
   // heads [mean | log_std] (2A <= 32 columns), K split over the waves; y over the first 2A
   // columns of the tile
-  if constexpr (MT == 2 && LBSIM_SAC_SPLIT_M)
+  if constexpr (MT == 2)
     splitk_out_m2(lds, ld, p.wh, p.bh, F / 16, (2 * p.A + 15) / 16, lds + R * ld, lds, ld,
                   2 * p.A, wave, lane);
   else
@@ -554,32 +544,6 @@ struct QmixMixAct {
 // tiles, <= 2 second-layer tiles each instead of 4 / 3 on waves 0-3), the second layer's first
 // weight blocks are requested before the first layer's barrier, and the ELU tail runs one thread
 // per (row, embedding unit) with a 32-lane sum (it ran 4 threads per row on one wave: 4.1 us).
-#ifndef LBSIM_MIX_PRIME
-#define LBSIM_MIX_PRIME 1
-#endif
-// 1: the pair kernel's epsilon-greedy inside the mixer's first layer (no barrier of its own)
-#ifndef LBSIM_QMIX_EPS_IN_MIXER
-#define LBSIM_QMIX_EPS_IN_MIXER 1
-#endif
-// 1: the pair kernel's obs rows loaded straight into LDS and waited for after the GRU's hidden
-// pass, which then runs first (see qmix_agent_pair_kernel)
-#ifndef LBSIM_QMIX_ASYNC_OBS
-#define LBSIM_QMIX_ASYNC_OBS 1
-#endif
-// 1: the pair kernel's first GRU weights requested after its staging loads (A/B)
-#ifndef LBSIM_QMIX_PRIME_LATE
-#define LBSIM_QMIX_PRIME_LATE 0
-#endif
-// waves per SIMD the pair kernel is built for: 4 = two 8-wave workgroups per CU (<= 128 VGPRs)
-#ifndef LBSIM_QMIX_PAIR_WPE
-#define LBSIM_QMIX_PAIR_WPE 4
-#endif
-#ifndef LBSIM_MIX_NW
-#define LBSIM_MIX_NW 8
-#endif
-#ifndef LBSIM_MIX_TAIL
-#define LBSIM_MIX_TAIL 1
-#endif
 struct NoOp {
   __device__ void operator()() const {}
 };
@@ -623,7 +587,7 @@ __device__ __forceinline__ void qmix_mixer(const QmixArgs& p, float* lds, const 
     const int tt = t < n1 ? t : (t < n1 + n2 ? t - n1 : 0);
     w2p[j] = (const f4*)w + (size_t)tt * kb * 64;
     b2p[j] += tt * 16;
-    if (NW == 8 && LBSIM_MIX_PRIME && mw) {  // requested now: their latency hides behind the first layer
+    if (NW == 8 && mw) {  // requested now: their latency hides behind the first layer
       pb0[j] = w2p[j][lane];
       pb1[j] = w2p[j][(kb > 1 ? 64 : 0) + lane];
     }
@@ -647,7 +611,7 @@ __device__ __forceinline__ void qmix_mixer(const QmixArgs& p, float* lds, const 
       const float bv = b2p[j][lane & 15];
 #pragma unroll
       for (int m = 0; m < MT; ++m) acc[j][m] = splat4(bv);
-      if (NW == 8 && LBSIM_MIX_PRIME)
+      if (NW == 8)
         mma_tile<MT>(acc[j], lds, ld, c2[j], w2p[j], kb, lane, pb0[j], pb1[j]);
       else
         mma_tile<MT>(acc[j], lds, ld, c2[j], w2p[j], kb, lane);
@@ -672,7 +636,7 @@ __device__ __forceinline__ void qmix_mixer(const QmixArgs& p, float* lds, const 
   LB_PHASE(10);
   // tail: hidden_e = elu(b1_e + sum_a q_a |w1[a E + e]|), Q_tot = sum_e hidden_e |w2_e| + b2
   const int b1c = 3 * he, w2c = A * E, b2c = A * E + E;
-  if (LBSIM_MIX_TAIL && NW * 64 == R * 32 && E == 32) {
+  if (NW * 64 == R * 32 && E == 32) {
     // one thread per (row, unit): rows r = tid / 32 of the wave's two halves, a 32-lane sum
     const int r = (int)threadIdx.x >> 5, u = (int)threadIdx.x & 31;
     const float* row = lds + r * ld;
@@ -706,6 +670,12 @@ __device__ __forceinline__ void qmix_mixer(const QmixArgs& p, float* lds, const 
     acc += __shfl_xor(acc, 2);
     if (part == 0 && row0 + r < p.B) p.q_tot[row0 + r] = acc + row[b2c];
   }
+}
+
+// LDS bytes of qmix_policy_kernel<MT>: the [R][ld] tile, qv, chosen and the split-K scratch.
+inline size_t qmix_policy_lds_bytes(int mt, int ld, int A) {
+  const size_t R = 16 * (size_t)mt;
+  return (R * ld + (size_t)A * R * 16 + R * A + 64 * R) * 4;
 }
 
 template <int MT, int H, int F>
@@ -787,6 +757,11 @@ __global__ void __launch_bounds__(256) qmix_policy_kernel(QmixArgs p) {
 // its agent's whole network in its own LDS region [16][lda] with no workgroup barrier between
 // layers, every layer's tiles in mma_multi passes (the GRU's three gates per unit tile, fc1 / fc2
 // four tiles at a time); the workgroup meets once, for the mixer.
+// LDS bytes of qmix_agent_wave_kernel: the four waves' [16][lda] regions, qv and chosen.
+inline size_t qmix_wave_lds_bytes(int lda, int A) {
+  return ((size_t)4 * 16 * lda + (size_t)A * 16 * 16 + 16 * (size_t)A) * 4;
+}
+
 template <int H, int F>
 __global__ void __launch_bounds__(256) qmix_agent_wave_kernel(QmixArgs p) {
   const uint32_t step = p.step_dev != nullptr ? *p.step_dev : p.step;
@@ -917,8 +892,19 @@ __global__ void __launch_bounds__(256) qmix_agent_wave_kernel(QmixArgs p) {
 // [h NT/2, (h+1) NT/2); fc3's k-blocks split in halves and summed), so 8192 envs give 4096 waves --
 // four per SIMD instead of two to hide the MFMA and L2 latency.  The pair shares the agent's LDS
 // region; every layer boundary is a workgroup barrier (all agents run the same layer sequence).
+// waves per SIMD the pair kernel is built for: 4 = two 8-wave workgroups per CU (<= 128 VGPRs)
+constexpr int kQmixPairWavesPerSimd = 4;
+// waves of the pair kernel's workgroup that run the mixer's GEMM layers (qmix_mixer's NW)
+constexpr int kQmixMixWaves = 8;
+
+// LDS bytes of qmix_agent_pair_kernel: the four agents' [16][lda] regions, qv, chosen, the fc3
+// partials and (sld > 0) the mixer's prefetched [16][sld] state rows.
+inline size_t qmix_pair_lds_bytes(int lda, int A, int sld) {
+  return ((size_t)4 * 16 * lda + 2 * (size_t)A * 16 * 16 + 16 * (size_t)A + (size_t)16 * sld) * 4;
+}
+
 template <int H, int F>
-__global__ void __launch_bounds__(512, LBSIM_QMIX_PAIR_WPE) qmix_agent_pair_kernel(QmixArgs p) {
+__global__ void __launch_bounds__(512, kQmixPairWavesPerSimd) qmix_agent_pair_kernel(QmixArgs p) {
   const uint32_t step = p.step_dev != nullptr ? *p.step_dev : p.step;
   extern __shared__ float lds[];
   constexpr int R = 16, UT = H / 16, NT = F / 16;
@@ -942,19 +928,19 @@ __global__ void __launch_bounds__(512, LBSIM_QMIX_PAIR_WPE) qmix_agent_pair_kern
     wx[1] = wi + (size_t)u * kbx * 64;
     wx[2] = wi + (size_t)(UT + u) * kbx * 64;
   };
-  // the first GRU pass's weights, the epsilon-greedy draw (independent of the network) and the
-  // mixer's state rows go out first: their latency hides behind the staging
-  BPrime<3> bp_gru;
   auto gru_wy = [&](int u, const f4* (&wy)[3]) {
     wy[0] = wh + (size_t)u * UT * 64;
     wy[1] = wh + (size_t)(UT + u) * UT * 64;
     wy[2] = wh + (size_t)(2 * UT + u) * UT * 64;
   };
-  if (!LBSIM_QMIX_PRIME_LATE) {
-    const f4* wx[3];
-    if (LBSIM_QMIX_ASYNC_OBS) gru_wy(h, wx);  // the hidden pass runs first
-    else gru_wx(h, wx);
-    bp_gru = mma_prime<3>(wx, LBSIM_QMIX_ASYNC_OBS ? UT : kbx, lane);
+  // the first GRU pass's weights (the hidden pass runs first), the epsilon-greedy draw
+  // (independent of the network) and the mixer's state rows go out first: their latency hides
+  // behind the staging
+  BPrime<3> bp_gru;
+  {
+    const f4* wy[3];
+    gru_wy(h, wy);
+    bp_gru = mma_prime<3>(wy, UT, lane);
   }
   u32x4 eps_d{};
   if (h == 0 && lane < R)
@@ -968,11 +954,11 @@ __global__ void __launch_bounds__(512, LBSIM_QMIX_PAIR_WPE) qmix_agent_pair_kern
   // waited for every earlier load, profiles/r06m/ r06n/)
   static_assert(128 % H == 0 && R * H % 128 == 0, "hidden staging: whole rows per thread group");
   constexpr int RH = R * H / 128;  // hidden rows per thread
-  // LBSIM_QMIX_ASYNC_OBS: the obs rows go straight into LDS (global_load_lds, no VGPRs) when a
-  // row is whole 64-column blocks (I == kxp, a multiple of 64, <= 128: 4 x 4's 128), and are waited
-  // for only before the GRU's input pass -- the hidden pass runs first, on the hidden rows staged
-  // below, while the obs rows (2/3 of the 27.6 MB burst at 8192 x 16) are still arriving
-  const bool obs_async = LBSIM_QMIX_ASYNC_OBS && p.I == kxp && kxp % 64 == 0 && kxp <= 128;
+  // the obs rows go straight into LDS (global_load_lds, no VGPRs) when a row is whole 64-column
+  // blocks (I == kxp, a multiple of 64, <= 128: 4 x 4's 128), and are waited for only before the
+  // GRU's input pass -- the hidden pass runs first, on the hidden rows staged below, while the obs
+  // rows (2/3 of the 27.6 MB burst at 8192 x 16) are still arriving
+  const bool obs_async = p.I == kxp && kxp % 64 == 0 && kxp <= 128;
   if (obs_async) {
     typedef __attribute__((address_space(1))) void gvoid;
     typedef __attribute__((address_space(3))) void lvoid;
@@ -1019,12 +1005,6 @@ __global__ void __launch_bounds__(512, LBSIM_QMIX_PAIR_WPE) qmix_agent_pair_kern
     const bool ok = e < tots && c < p.Ds && b < p.B;
     sat[k] = e < tots ? (ok ? r * p.sld + c : -(r * p.sld + c) - 1) : INT32_MIN;
     vs[k] = p.state[bc * p.Ds + (ok ? c : 0)];
-  }
-  if (LBSIM_QMIX_PRIME_LATE) {  // the weights after the HBM rows (every workgroup reads the same
-    const f4* wx[3];            // lines: L2-channel hot spots)
-    if (LBSIM_QMIX_ASYNC_OBS) gru_wy(h, wx);
-    else gru_wx(h, wx);
-    bp_gru = mma_prime<3>(wx, LBSIM_QMIX_ASYNC_OBS ? UT : kbx, lane);
   }
   // the reset bytes last: their compares (hoisted into the branch) wait for every load above,
   // which are all in flight by then -- one HBM round trip for the whole staging
@@ -1082,19 +1062,14 @@ __global__ void __launch_bounds__(512, LBSIM_QMIX_PAIR_WPE) qmix_agent_pair_kern
     gru_wx(u, wx);
     const f4* wy[3];
     gru_wy(u, wy);
-    if (LBSIM_QMIX_ASYNC_OBS) {  // hidden part first (r, z, n_h), then the input part
-      mma_multi<1, 3>(*reinterpret_cast<f4(*)[3][1]>(&g[1]), mine, lda, kxp, wy, UT, lane,
-                      uu == 0 ? bp_gru : mma_prime<3>(wy, UT, lane));
-      if (uu == 0 && obs_async) {  // the obs rows landed in LDS, every wave's
-        __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
-        __syncthreads();
-      }
-      mma_multi<1, 3>(*reinterpret_cast<f4(*)[3][1]>(&g[0]), mine, lda, 0, wx, kbx, lane);
-    } else {
-      mma_multi<1, 3>(*reinterpret_cast<f4(*)[3][1]>(&g[0]), mine, lda, 0, wx, kbx, lane,
-                      uu == 0 ? bp_gru : mma_prime<3>(wx, kbx, lane));
-      mma_multi<1, 3>(*reinterpret_cast<f4(*)[3][1]>(&g[1]), mine, lda, kxp, wy, UT, lane);
+    // hidden part first (r, z, n_h), then the input part
+    mma_multi<1, 3>(*reinterpret_cast<f4(*)[3][1]>(&g[1]), mine, lda, kxp, wy, UT, lane,
+                    uu == 0 ? bp_gru : mma_prime<3>(wy, UT, lane));
+    if (uu == 0 && obs_async) {  // the obs rows landed in LDS, every wave's
+      __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);
+      __syncthreads();
     }
+    mma_multi<1, 3>(*reinterpret_cast<f4(*)[3][1]>(&g[0]), mine, lda, 0, wx, kbx, lane);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float hp = mine[(4 * (lane >> 4) + i) * lda + kxp + col];
@@ -1178,7 +1153,7 @@ __global__ void __launch_bounds__(512, LBSIM_QMIX_PAIR_WPE) qmix_agent_pair_kern
   LB_PHASE(7);
   // epsilon-greedy for (env lane, agent a), as qmix_policy_kernel.  Its results (chosen) are read
   // only by the mixer's tail, so it runs inside the mixer's first layer, after that layer's GEMM
-  // and before its barrier (LBSIM_QMIX_EPS_IN_MIXER; it had a barrier interval of its own)
+  // and before its barrier (it had a barrier interval of its own)
   auto eps_greedy = [&]() {
     if (h == 0 && lane < R) {
       const int r = lane;
@@ -1201,17 +1176,9 @@ __global__ void __launch_bounds__(512, LBSIM_QMIX_PAIR_WPE) qmix_agent_pair_kern
       }
     }
   };
-  if (!LBSIM_QMIX_EPS_IN_MIXER) {
-    eps_greedy();
-    __syncthreads();
-  }
   LB_PHASE(8);
-  if (LBSIM_QMIX_EPS_IN_MIXER)
-    qmix_mixer<1, LBSIM_MIX_NW>(p, lds, chosen, row0, wave, lane, p.sld > 0 ? pre : nullptr,
-                                p.sld, eps_greedy);
-  else
-    qmix_mixer<1, LBSIM_MIX_NW>(p, lds, chosen, row0, wave, lane, p.sld > 0 ? pre : nullptr,
-                                p.sld);
+  qmix_mixer<1, kQmixMixWaves>(p, lds, chosen, row0, wave, lane, p.sld > 0 ? pre : nullptr, p.sld,
+                               eps_greedy);
   LB_PHASE(11);
 }
 

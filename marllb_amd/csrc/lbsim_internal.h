@@ -1,9 +1,10 @@
 // lbsim_internal.h — host-side glue between the extern "C" API (lbsim_api.hip) and the translation
 // units that instantiate the templated kernels (compiled in parallel, linked into liblbsim.so):
 //
-//   lbsim_dyn.hip      dynamics_kernel / dynamics_group_kernel launchers; built twice
-//                      (-DLBSIM_DYN_MODE=0: step, 1: reset)
+//   lbsim_dyn.hip      dynamics_kernel / dynamics_group_kernel launchers; built three times
+//                      (-DLBSIM_DYN_MODE=0: step, 1: reset, 2: the next-step auto-reset step)
 //   lbsim_obs.hip      observe_kernel launchers
+//   lbsim_step.hip     the one-launch steps (fused_step_kernel, step_wave_kernel)
 //   lbsim_pol.hip      one-kernel policy networks (lbsim_fused.h)
 //
 // Non-template kernels live only in lbsim_api.hip (a __global__ defined in two objects would be
@@ -11,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdlib>
 
 #include "../../include/lbsim.h"
@@ -28,6 +30,13 @@ void note_launch(const void* host_fn);
     ::lbk::note_launch(reinterpret_cast<const void*>(&KERNEL));           \
     hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);    \
   } while (0)
+
+// An integer override from the environment (tests, bench.py and the A/B tools set these), else
+// dflt.  Callers keep the value in a function-local static: read once per process.
+inline int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : dflt;
+}
 
 // What a launcher needs of a handle.
 struct LaunchCtx {
@@ -50,10 +59,7 @@ inline int dyn_group_lanes(const LaunchCtx& L) {
   // (split lost-FIN handles and reservoir_mode VPP run the server-per-lane kernel only)
   if (L.dyn_mapping == LBSIM_DYN_ENV_PER_LANE && L.S <= 16 && !L.prm.split && !L.prm.res_vpp)
     return 0;
-  static const int forced = [] {
-    const char* e = std::getenv("LBSIM_DYN_GROUP_LANES");
-    return e ? std::atoi(e) : 0;
-  }();
+  static const int forced = env_int("LBSIM_DYN_GROUP_LANES", 0);
   if (forced >= L.S && (forced == 4 || forced == 8 || forced == 16 || forced == 32 || forced == 64))
     return forced;
   if (L.S <= 2) return 2;
@@ -69,19 +75,16 @@ inline int dyn_group_lanes(const LaunchCtx& L) {
 // Measured dynamics, wave vs server-per-lane groups (profiles/r03w/wave_sweep*.txt): S = 4 1024
 // envs 0.041 vs 0.084 ms, 4096 0.066 vs 0.090, 8192 0.108 vs 0.095 (8 waves per SIMD:
 // issue-bound, the groups win); S = 8 2048 envs 0.058 vs 0.078, 4096 0.087 vs 0.083.
-// LBSIM_DYN_WAVE_MAX_B overrides the limit; LBSIM_DYN_WAVE = 0 disables the kernel, 1 uses it at
-// every batch size it applies to; a forced LBSIM_DYN_GROUP_LANES width wins over both.
+// LBSIM_DYN_WAVE = 0 disables the kernel, 1 uses it at every batch size it applies to; a forced
+// LBSIM_DYN_GROUP_LANES width wins over it.
 inline int dyn_wave_mode() {
-  static const int mode = [] {
-    const char* e = std::getenv("LBSIM_DYN_WAVE");
-    return e ? std::atoi(e) : -1;
-  }();
+  static const int mode = env_int("LBSIM_DYN_WAVE", -1);
   return mode;
 }
 
 // Whether the wave dynamics can serve this handle at all (batch size aside).
 inline bool dyn_wave_fits(const LaunchCtx& L) {
-  static const bool forced_lanes = std::getenv("LBSIM_DYN_GROUP_LANES") != nullptr;
+  static const bool forced_lanes = env_int("LBSIM_DYN_GROUP_LANES", INT_MIN) != INT_MIN;  // set
   if (dyn_wave_mode() == 0 || forced_lanes || L.dyn_mapping == LBSIM_DYN_ENV_PER_LANE) return false;
   if (L.S > 8 || L.prm.Q > 32 || L.prm.policy == LBSIM_POLICY_ALIAS) return false;
   // server failures, n_flow_on_mode VPP's lost-flow counts: the group / env-lane kernels; lost-FIN
@@ -90,14 +93,10 @@ inline bool dyn_wave_fits(const LaunchCtx& L) {
 }
 
 inline bool dyn_wave_ok(const LaunchCtx& L) {
-  static const int64_t max_b = [] {
-    const char* e = std::getenv("LBSIM_DYN_WAVE_MAX_B");
-    return e ? (int64_t)std::atoll(e) : (int64_t)-1;
-  }();
   if (!dyn_wave_fits(L)) return false;
   const int mode = dyn_wave_mode();
   const int64_t per_simd = L.S <= 4 ? 4 : 2;  // S = 8: 2048 envs 0.058 vs 0.078 ms, 4096 0.087 vs 0.083
-  return mode == 1 || (int64_t)L.B <= (max_b >= 0 ? max_b : per_simd * (int64_t)L.simds);
+  return mode == 1 || (int64_t)L.B <= per_simd * (int64_t)L.simds;
 }
 
 // Dynamics of one step (mode kModeStep) or of a reset with warm-up (kModeReset).
@@ -126,8 +125,13 @@ bool launch_fused_step(const LaunchCtx& L, int group_lanes, const void* action, 
 void launch_step_wave(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
                       const ObsOutputs& o, hipStream_t s);
 
-// the fused policy kernels (lbsim_pol.hip): LBSIM_OK / LBSIM_EDEVICE / LBSIM_ENOTSUP
-int launch_sac_actor(SacActorArgs& a, int64_t B, int mt, size_t lds, hipStream_t s);
-int launch_qmix_policy(QmixArgs& a, int64_t B, int form, int mt, size_t lds, hipStream_t s);
+// The fused policy kernels (lbsim_pol.hip), which own their LDS layout: the launchers set the
+// args' row strides (ld, lda, sld), halve the wanted tile size mt (1 | 2 | 4: 16 mt envs per
+// workgroup) until its LDS fits, and launch.  LBSIM_OK / LBSIM_EDEVICE / LBSIM_ENOTSUP.
+int launch_sac_actor(SacActorArgs& a, int64_t B, int mt, hipStream_t s);
+// form: 0 = layer-split tile kernel, 1 = one wave per agent, 2 = two waves per agent where the
+// kernel has that form (A = 4), else one; forms 1 and 2 need mt = 1 after the back-off, else the
+// tile kernel runs.
+int launch_qmix_policy(QmixArgs& a, int64_t B, int form, int mt, hipStream_t s);
 
 }  // namespace lbk

@@ -1846,7 +1846,7 @@ __device__ __forceinline__ bool observe_chunk_full(const DevState& st, const Sim
 // REGS = false: the general path only -- observe_rows_paired's fallback for rows the register
 // path cannot take (one copy of the code instead of two more register-path instantiations: fewer
 // SGPR / VGPR spills in observe_pair_kernel, 131 -> 125 us at 65536 x 4, 241 -> 229 us at
-// 65536 x 8, profiles/r05f/; LBSIM_OBS_PAIR_FALLBACK_REGS=1 restores the full observe_chunk).
+// 65536 x 8, profiles/r05f/).
 // The general path of observe_chunk (LDS image of the reservoirs) for servers [s_base, s_base +
 // S) of env b.  Split handles (lost-FIN, DevState::res_count_dur) give the duration reservoir its
 // own count and timestamps, hence its own decay weights: reservoir r then uses weight row r (S <= 2
@@ -2496,9 +2496,6 @@ __device__ __forceinline__ void observe_rows_paired_regs(const DevState& st, con
 // INC: unchanged rows take their cached features unless some env was reset by this step (nr:
 // next-step auto-reset is on; its ep_step words are loaded with the decision words); rows
 // the register path cannot take (n < 8, a sample >= kPackLimit) go through observe_chunk per env.
-#ifndef LBSIM_OBS_PAIR_FALLBACK_REGS
-#define LBSIM_OBS_PAIR_FALLBACK_REGS 0
-#endif
 template <bool INC>
 __device__ __forceinline__ void observe_rows_paired(const DevState& st, const SimParams& p,
                                                     size_t b0, int nenv, ObsScratch& sc,
@@ -2533,9 +2530,9 @@ __device__ __forceinline__ void observe_rows_paired(const DevState& st, const Si
   }
   for (int e = 0; e < nenv; ++e) {
     for (int s0 = 0; s0 < S; s0 += kObsChunk)
-      observe_chunk<true, INC, LBSIM_OBS_PAIR_FALLBACK_REGS != 0, false>(
-          st, p, b0 + (size_t)e, s0, S - s0 < kObsChunk ? S - s0 : kObsChunk, sc,
-          obs_out + e * S * NF, lane);
+      observe_chunk<true, INC, false, false>(st, p, b0 + (size_t)e, s0,
+                                             S - s0 < kObsChunk ? S - s0 : kObsChunk, sc,
+                                             obs_out + e * S * NF, lane);
   }
 }
 
@@ -2570,8 +2567,7 @@ __device__ __forceinline__ void observe_rows_paired_wide(const DevState& st, con
     return;
   }
   for (int c = s0; c < s0 + 8; c += kObsChunk)
-    observe_chunk<true, INC, LBSIM_OBS_PAIR_FALLBACK_REGS != 0, false>(st, p, b, c, kObsChunk, sc,
-                                                                 obs_env, lane);
+    observe_chunk<true, INC, false, false>(st, p, b, c, kObsChunk, sc, obs_env, lane);
 }
 
 // ================================================================ observe (one wave = one env)
@@ -2735,11 +2731,9 @@ __global__ void __launch_bounds__(64 * kObsWavesPerEnv<MAXS>, 5)
 // episode words and outputs (observe_outputs, in env order).
 // 4 waves per SIMD (128 VGPRs): with 5 (96 VGPRs) the register path spilled and the kernel ran
 // 140 us against 130 us at 65536 x 4, 255 against 236 us at 65536 x 8 (profiles/r05d/).
-#ifndef LBSIM_OBS_PAIR_WAVES
-#define LBSIM_OBS_PAIR_WAVES 4
-#endif
+constexpr int kObsPairWaves = 4;
 template <int MODE, bool FAC>
-__global__ void __launch_bounds__(64, LBSIM_OBS_PAIR_WAVES)
+__global__ void __launch_bounds__(64, kObsPairWaves)
     observe_pair_kernel(DevState st, SimParams p, ObsOutputs out) {
   __shared__ ObsScratch sc;
   __shared__ float s_obs[8 * NF];
@@ -2760,11 +2754,9 @@ __global__ void __launch_bounds__(64, LBSIM_OBS_PAIR_WAVES)
 // workgroup of two waves per env, wave w observing rows [8 w, 8 w + 8) (observe_rows_paired_wide),
 // then the env's reward, episode words and outputs (observe_outputs) -- the work of
 // observe_kernel<16>'s four chunk waves in two.
-#ifndef LBSIM_OBS_PAIR16_WAVES
-#define LBSIM_OBS_PAIR16_WAVES LBSIM_OBS_PAIR_WAVES
-#endif
+constexpr int kObsPair16Waves = kObsPairWaves;
 template <int MODE, bool FAC>
-__global__ void __launch_bounds__(128, LBSIM_OBS_PAIR16_WAVES)
+__global__ void __launch_bounds__(128, kObsPair16Waves)
     observe_pair16_kernel(DevState st, SimParams p, ObsOutputs out) {
   __shared__ ObsScratch sc[2];
   __shared__ float s_obs[16 * NF];
@@ -2779,7 +2771,7 @@ __global__ void __launch_bounds__(128, LBSIM_OBS_PAIR16_WAVES)
 // The raw rows of paired-record wide envs (S > 16, a multiple of 8) for observe_rows_kernel: one
 // single-wave workgroup per (env, 8-row group), as observe_chunks_kernel per 4-server chunk.
 template <int MODE>
-__global__ void __launch_bounds__(64, LBSIM_OBS_PAIR_WAVES)
+__global__ void __launch_bounds__(64, kObsPairWaves)
     observe_pair_chunks_kernel(DevState st, SimParams p, ObsOutputs out, int ngroups) {
   const size_t b = blockIdx.x / (unsigned)ngroups;
   const int c = (int)(blockIdx.x - b * (unsigned)ngroups);
@@ -2823,9 +2815,6 @@ __global__ void __launch_bounds__(64)
 
 // observe_kernel's work for env b by ONE wave, its chunks in sequence (fused_step_kernel's second
 // phase).  Same routines, same order: the same bits.
-#ifndef LBSIM_STEP_WAVE_PAIRED
-#define LBSIM_STEP_WAVE_PAIRED 1
-#endif
 template <int MAXS>
 __device__ __forceinline__ void observe_env_wave(const DevState& st, const SimParams& p,
                                                  const ObsOutputs& out, size_t b, ObsScratch& sc,
@@ -2833,7 +2822,7 @@ __device__ __forceinline__ void observe_env_wave(const DevState& st, const SimPa
   const int S = p.S;
   if constexpr (MAXS <= kObsChunk) {  // one chunk: straight-line code, no loop-carried s0
     observe_chunk<true, true, true, false>(st, p, b, 0, S, sc, s_obs, lane);
-  } else if (LBSIM_STEP_WAVE_PAIRED && MAXS <= 8 && st.res_dur == nullptr) {
+  } else if (MAXS <= 8 && st.res_dur == nullptr) {
     // paired records: the env's S <= 8 rows in one pass (observe_rows_paired)
     observe_rows_paired<true>(st, p, b, 1, sc, s_obs, lane);
   } else {

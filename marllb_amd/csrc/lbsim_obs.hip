@@ -1,8 +1,5 @@
 // lbsim_obs.hip — observe launchers: one wave per 4-server chunk, the chunks of an
 // env in one workgroup, each with its own ObsScratch in dynamic LDS.
-#include <cstdlib>
-#include <cstring>
-
 #include "lbsim_internal.h"
 
 namespace lbk {
@@ -34,15 +31,9 @@ void launch_observe_t(const LaunchCtx& L, const ObsOutputs& o, const uint8_t* ma
                        mask);
 }
 
-// Envs of more than LBSIM_OBSERVE_SPLIT_S servers (default 16) observe in two launches
-// (observe_chunks_kernel + observe_rows_kernel) instead of one workgroup of S / 4 waves per env.
-int observe_split_s() {
-  static const int v = [] {
-    const char* e = std::getenv("LBSIM_OBSERVE_SPLIT_S");
-    return e ? std::atoi(e) : 16;
-  }();
-  return v;
-}
+// Envs of more than kObserveSplitS servers observe in two launches (observe_chunks_kernel +
+// observe_rows_kernel) instead of one workgroup of S / 4 waves per env.
+constexpr int kObserveSplitS = 16;
 
 template <int MODE, bool FAC>
 void launch_observe_split(const LaunchCtx& L, const ObsOutputs& o, const uint8_t* mask,
@@ -61,14 +52,9 @@ void launch_observe_split(const LaunchCtx& L, const ObsOutputs& o, const uint8_t
 
 // The paired step observe (observe_pair_kernel): no duration plane (duration == fct by
 // construction: duration_mode AGE, lost-FIN off) and S <= 8 (8 / S whole envs per wave), or S a
-// multiple of 8 (S / 8 waves per env: observe_pair16_kernel, observe_pair_chunks_kernel).  LBSIM_OBSERVE_PAIRED=0
-// turns it off (A/B; the same bits either way).
+// multiple of 8 (S / 8 waves per env: observe_pair16_kernel, observe_pair_chunks_kernel).
 bool observe_paired(const LaunchCtx& L) {
-  static const bool on = [] {
-    const char* e = std::getenv("LBSIM_OBSERVE_PAIRED");
-    return !(e != nullptr && std::strcmp(e, "0") == 0);
-  }();
-  return on && L.st.res_dur == nullptr && (L.S <= 8 || L.S % 8 == 0);
+  return L.st.res_dur == nullptr && (L.S <= 8 || L.S % 8 == 0);
 }
 
 // the problem-05 facade rows (agent_obs / state) come from their own instantiation
@@ -108,7 +94,7 @@ void launch_observe_m(const LaunchCtx& L, const ObsOutputs& o, const uint8_t* ma
       LBSIM_LAUNCH((observe_pair_kernel<MODE, false>), grid, block, 0, stream, L.st, L.prm, o);
     return;
   }
-  if (L.S > kObsChunk && L.S > observe_split_s()) {
+  if (L.S > kObsChunk && L.S > kObserveSplitS) {
     if (fac) launch_observe_split<MODE, true>(L, o, mask, stream);
     else launch_observe_split<MODE, false>(L, o, mask, stream);
     return;

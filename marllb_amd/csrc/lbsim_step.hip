@@ -102,10 +102,7 @@ void launch_wo(const LaunchCtx& L, const void* action, int dtype, int32_t* assig
 template <int NG, int POLICY>
 void launch_w(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
               const ObsOutputs& o, hipStream_t s) {
-  static const int forced = [] {
-    const char* e = std::getenv("LBSIM_STEP_WAVE_OCC");
-    return e ? std::atoi(e) : 0;
-  }();
+  static const int forced = env_int("LBSIM_STEP_WAVE_OCC", 0);
   const bool occ2 = forced == 2 || (forced != 4 && (int64_t)L.B <= 2 * (int64_t)L.simds);
   if (occ2) launch_wo<NG, POLICY, 2>(L, action, dtype, assign, o, s);
   else launch_wo<NG, POLICY, 4>(L, action, dtype, assign, o, s);

@@ -117,6 +117,31 @@ def test_sac_actor_kernel_matches_module(g):
 
 
 @pytest.mark.gpu
+def test_sac_actor_kernel_wide_state_matches_module():
+    """state_dim 500 (padded to 512: an LDS row stride of 644 floats): the 64-env tile would need
+    177 KB of LDS there, so with LBSIM_FUSED_MT=4 (test_other_tile_forms_match_modules) the
+    launcher backs off to the 32-env tile -- the same results as the torch module at every forced
+    tile size.  B = 17: one full 16-env tile plus a ragged one; reset rows."""
+    dev = "cuda:0"
+    torch.manual_seed(13)
+    pol = GRUPolicy(500, 8, 256, 128).to(dev)
+    gen = torch.Generator(device=dev).manual_seed(6)
+    B = 17
+    x = torch.randn(B, 500, device=dev, generator=gen) * 0.3
+    h = torch.randn(B, 128, device=dev, generator=gen) * 0.5
+    mask = torch.zeros(B, dtype=torch.bool, device=dev)
+    mask[::5] = True
+    with torch.no_grad():
+        mean, log_std, rh = pol(x, (h * (~mask).unsqueeze(1)).unsqueeze(0))
+    f = FusedGRUPolicy(pol)
+    assert f.kernel is not None
+    a, h1, ls = f(x, h, deterministic=True, reset_mask=mask)
+    close(a, torch.tanh(mean))
+    close(h1, rh[0])
+    close(ls, log_std)
+
+
+@pytest.mark.gpu
 def test_qmix_policy_kernel_matches_modules(g):
     dev = "cuda:0"
     agents = [load_prefixed(AgentQNet(128, 3, 128, 64), g, "agentq").to(dev) for _ in range(4)]

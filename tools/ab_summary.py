@@ -1,4 +1,4 @@
-"""Summarise an A/B jsonl written by tools/gpu_lib_ab.sh / gpu_obs_ab.sh: value and kernel times."""
+"""Summarise an A/B jsonl written by tools/gpu_lib_ab.sh: value and kernel times."""
 import json
 import sys
 
