@@ -425,6 +425,34 @@ int lbsim_set_trace(lbsim_t* h, const uint32_t* gap_us, const float* work, int64
 int lbsim_alias_tables(const float* weights, int64_t n, int S, float* odd_out, int32_t* alias_out,
                        int32_t* active_out, void* stream);
 
+/* ---- per-env workload (domain randomisation) ----
+ * lbsim_set_env_rates: arrival_rate[B] flows/s and/or server_rate[B, S] flows/s (f32 DEVICE
+ * pointers, either may be NULL = leave that one as it is).  Converted (1e6 / rate, divided in f64
+ * and rounded once to f32, as the config's own rates are) into handle-owned device arrays that
+ * every later dynamics launch of this handle (step, reset, warm-up) reads in place of the config's
+ * shared arrival_rate / server_rate[]: from the next launch on every arrival gap drawn and every
+ * service time computed uses the env's own rate; the next arrival already drawn keeps its time
+ * and work.  Ranges are the config's (arrival in [0.1, 1e6], server in [1, 1e7], NaN rejected):
+ * the call waits on `stream`, and with any value out of range returns LBSIM_EINVAL (the count in
+ * lbsim_last_error) and leaves the previous rates in force.  LBSIM_ENOTSUP: a non-NULL
+ * arrival_rate on a lost-FIN handle (lost_fin_prob > 0: the bucket-wait mean and the signed 32-bit
+ * bound of lbsim_config_validate depend on the arrival rate) or on a TRACE handle (the trace sets
+ * the rate); server_rate is allowed on both.
+ * The arrays are allocated by the first call and never moved; later calls rewrite them in place,
+ * so a step captured into a hipGraph AFTER the first call sees later updates on replay (the first
+ * call allocates and synchronises: it must precede the capture).  lbsim_step / lbsim_reset gain
+ * no synchronisation and no allocation.  The rates are NOT part of the snapshot
+ * (lbsim_get_state / lbsim_set_state): a handle that loads a state keeps its own rates.
+ * lbsim_clear_env_rates: back to the config's shared rates (waits for the device; the handle's
+ * arrays take the config's values, so a graph captured while rates were set replays with those).
+ * lbsim_get_env_rates: the current effective rates into device buffers [B] / [B, S] (either may
+ * be NULL), the config's values when no per-env rates are set. */
+int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* server_rate,
+                        void* stream);
+int lbsim_clear_env_rates(lbsim_t* h);
+int lbsim_get_env_rates(lbsim_t* h, float* arrival_rate_out, float* server_rate_out,
+                        void* stream);
+
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/
  * alias_table.h:82-158, alias_table_build, rebuilt by lb_rl_node.c:92-111 from the weights the

@@ -6,9 +6,10 @@ liblbsim.so), with the reference's Gym-style API on top.
 """
 from .env import FEATURE_NAMES, LoadBalanceEnv, LoadBalanceEnvGym, VecLoadBalanceEnv, make_config
 from .multi_agent import MultiAgentLoadBalanceEnv, VecMultiAgentLoadBalanceEnv
+from .randomize import sample_rates
 from .spaces import Box, MultiDiscrete
 
 __all__ = ["FEATURE_NAMES", "LoadBalanceEnv", "LoadBalanceEnvGym", "VecLoadBalanceEnv",
            "MultiAgentLoadBalanceEnv", "VecMultiAgentLoadBalanceEnv", "make_config", "Box",
-           "MultiDiscrete"]
+           "MultiDiscrete", "sample_rates"]
 __version__ = "0.1.0"

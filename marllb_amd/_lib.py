@@ -169,6 +169,9 @@ _SIGNATURES = {
     "lbsim_agent_obs": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, _P, _P]),
     "lbsim_set_trace": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, _P]),
+    "lbsim_set_env_rates": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lbsim_clear_env_rates": (ctypes.c_int, [_P]),
+    "lbsim_get_env_rates": (ctypes.c_int, [_P, _P, _P, _P]),
     "lbsim_alias_tables": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P]),
     "lbsim_vose_tables": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P]),
     "lbsim_vose_sample": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, _P, ctypes.c_int64,

@@ -71,6 +71,8 @@ struct lbsim {
   std::vector<void*> allocs;
   void* trace_buf = nullptr;  // gap_us[rows] then work[rows]
   unsigned long long* stats_buf = nullptr;  // lbsim_step_stats sums (2 x u64)
+  // lbsim_set_env_rates: one block, allocated by the first call and never moved (EnvRates below)
+  float* rates_buf = nullptr;
   bool initialised;  // a full reset has been issued
   std::string err;
   // (class, host stub) of the kernels the last lbsim_step_ex / lbsim_reset_ex launched
@@ -317,10 +319,92 @@ __global__ void copy_episode_stats(const int32_t* steps, const double* ret, int3
   if (ro) ro[i] = ret[i];
 }
 
+// Per-env rates (lbsim_set_env_rates).  The handle's block holds, in floats: the live arrays the
+// kernels and lbsim_get_env_rates read -- arrival[B], server[B*S] (flows/s as given), gap[B],
+// scale[B*S] (us, what the event loops consume) -- then staging copies of the four (a call
+// converts into these and only a valid one is copied over the live arrays), the config's own
+// rates {arrival, server[MAX_S]}, and the offender count (one u32).
+struct EnvRates {
+  float *arrival, *server, *gap, *scale;
+};
+EnvRates env_rates_at(float* base, size_t B, size_t BS) {
+  return EnvRates{base, base + B, base + B + BS, base + 2 * B + BS};
+}
+EnvRates env_rates_live(const lbsim_t* h) {
+  return env_rates_at(h->rates_buf, (size_t)h->B, (size_t)h->B * h->S);
+}
+EnvRates env_rates_staging(const lbsim_t* h) {
+  const size_t B = (size_t)h->B, BS = B * h->S;
+  return env_rates_at(h->rates_buf + 2 * (B + BS), B, BS);
+}
+float* env_rates_defaults(const lbsim_t* h) {
+  return h->rates_buf + 4 * ((size_t)h->B + (size_t)h->B * h->S);
+}
+uint32_t* env_rates_bad(const lbsim_t* h) {
+  return reinterpret_cast<uint32_t*>(env_rates_defaults(h) + 1 + MAX_S);
+}
+
+// Rates (flows/s) to the event loops' constants: mean_gap_us = 1e6 / rate and svc_scale = 1e6 / mu,
+// divided in f64 and rounded once to f32 as derive_params does (so an env given the config's own
+// rates computes the config's bits).  Element (b, s) of either input is in[b * stride + s]: the
+// caller's [B] / [B, S] arrays (strides 1, S) or the config's rates for every env (stride 0).
+// Values outside the config's ranges (NaN included) are counted into *bad.
+__global__ void __launch_bounds__(256)
+    env_rates_kernel(const float* arr_in, int64_t arr_stride, const float* srv_in,
+                     int64_t srv_stride, int B, int S, EnvRates out, uint32_t* bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t off = 0u;
+  if (srv_in != nullptr && i < (int64_t)B * S) {
+    const int64_t b = i / S;
+    const float mu = srv_in[b * srv_stride + (i - b * S)];
+    off += (!(mu >= 1.0f) || !(mu <= 1.0e7f)) ? 1u : 0u;
+    out.server[i] = mu;
+    out.scale[i] = (float)(1e6 / (double)mu);
+  }
+  if (arr_in != nullptr && i < (int64_t)B) {
+    const float r = arr_in[i * arr_stride];
+    off += (!(r >= 0.1f) || !(r <= 1.0e6f)) ? 1u : 0u;
+    out.arrival[i] = r;
+    out.gap[i] = (float)(1e6 / (double)r);
+  }
+  for (int d = 32; d > 0; d >>= 1) off += __shfl_xor(off, d, 64);
+  if ((threadIdx.x & 63) == 0 && off != 0u) atomicAdd(bad, off);
+}
+
 int launch_check(lbsim_t* h, const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, LBSIM_EDEVICE, "%s: %s", what, hipGetErrorString(e));
   return LBSIM_OK;
+}
+
+// The config's rates into the live per-env arrays (every env the same), on stream s.
+void env_rates_fill_defaults(lbsim_t* h, hipStream_t s) {
+  const float* def = env_rates_defaults(h);
+  const int64_t n = (int64_t)h->B * h->S;
+  hipLaunchKernelGGL(env_rates_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, def,
+                     (int64_t)0, def + 1, (int64_t)0, h->B, h->S, env_rates_live(h),
+                     env_rates_bad(h));
+}
+
+// The per-env rate block: allocated once, its live arrays holding the config's rates.
+int env_rates_ensure(lbsim_t* h, hipStream_t s) {
+  if (h->rates_buf != nullptr) return LBSIM_OK;
+  const size_t B = (size_t)h->B, BS = B * h->S;
+  const size_t bytes = (4 * (B + BS) + 1 + MAX_S) * sizeof(float) + sizeof(uint32_t);
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", bytes);
+  h->rates_buf = (float*)p;
+  float def[1 + MAX_S];
+  def[0] = h->cfg.arrival_rate;
+  for (int k = 0; k < MAX_S; ++k) def[1 + k] = k < h->S ? h->cfg.server_rate[k] : 1.0f;
+  if (hipMemcpy(env_rates_defaults(h), def, sizeof(def), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(env_rates_bad(h), 0, sizeof(uint32_t)) != hipSuccess) {
+    (void)hipFree(p);
+    h->rates_buf = nullptr;
+    return fail(h, LBSIM_EDEVICE, "per-env rates: upload of the config's rates failed");
+  }
+  env_rates_fill_defaults(h, s);
+  return launch_check(h, "env_rates_kernel");
 }
 
 // Brackets one launch with profiler events when profiling is on (class: see lbsim.h).
@@ -607,6 +691,7 @@ int lbsim_destroy(lbsim_t* h) {
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->trace_buf) (void)hipFree(h->trace_buf);
     if (h->stats_buf) (void)hipFree(h->stats_buf);
+    if (h->rates_buf) (void)hipFree(h->rates_buf);
     for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
   }
   delete h;
@@ -790,6 +875,86 @@ int lbsim_set_trace(lbsim_t* h, const uint32_t* gap_us, const float* work, int64
   h->st.trace_work = w_dev;
   h->prm.trace_rows = (uint32_t)rows;
   return LBSIM_OK;
+}
+
+int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* server_rate,
+                        void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (arrival_rate != nullptr && h->prm.lf_thr != 0u)
+    return fail(h, LBSIM_ENOTSUP, "per-env arrival rates on a lost-FIN handle (lost_fin_prob > 0): "
+                                  "the bucket-wait mean and the 32-bit guess bound depend on the "
+                                  "arrival rate (per-env server rates are allowed)");
+  if (arrival_rate != nullptr && h->prm.trace)
+    return fail(h, LBSIM_ENOTSUP, "per-env arrival rates on a TRACE handle: the trace sets the "
+                                  "arrival rate (per-env server rates are allowed)");
+  if (arrival_rate == nullptr && server_rate == nullptr) return LBSIM_OK;
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  int rc = env_rates_ensure(h, s);
+  if (rc != LBSIM_OK) return rc;
+  const size_t B = (size_t)h->B, BS = B * h->S;
+  const EnvRates live = env_rates_live(h), stg = env_rates_staging(h);
+  uint32_t* const bad = env_rates_bad(h);
+  if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "per-env rates: hipMemsetAsync failed");
+  hipLaunchKernelGGL(env_rates_kernel, dim3((unsigned)((BS + 255) / 256)), dim3(256), 0, s,
+                     arrival_rate, (int64_t)1, server_rate, (int64_t)h->S, h->B, h->S, stg, bad);
+  rc = launch_check(h, "env_rates_kernel");
+  if (rc != LBSIM_OK) return rc;
+  uint32_t nbad = 0;
+  if (hipMemcpyAsync(&nbad, bad, sizeof(nbad), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "per-env rates: conversion failed");
+  if (nbad != 0u)  // the live arrays are untouched: the previous rates stay in force
+    return fail(h, LBSIM_EINVAL, "per-env rates: %u value(s) out of range (arrival_rate must be in "
+                                 "[0.1, 1e6] flows/s, server_rate in [1, 1e7]; NaN rejected)", nbad);
+  bool ok = true;
+  if (arrival_rate != nullptr) {
+    ok &= hipMemcpyAsync(live.arrival, stg.arrival, B * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    ok &= hipMemcpyAsync(live.gap, stg.gap, B * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  }
+  if (server_rate != nullptr) {
+    ok &= hipMemcpyAsync(live.server, stg.server, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    ok &= hipMemcpyAsync(live.scale, stg.scale, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  }
+  if (!ok) return fail(h, LBSIM_EDEVICE, "per-env rates: device copy failed");
+  h->st.env_gap = live.gap;
+  h->st.env_scale = live.scale;
+  return LBSIM_OK;
+}
+
+int lbsim_clear_env_rates(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  h->st.env_gap = nullptr;
+  h->st.env_scale = nullptr;
+  if (h->rates_buf == nullptr) return LBSIM_OK;
+  // a step captured into a graph while the rates were set keeps reading the live arrays: they
+  // take the config's rates (no stream argument here, so the whole device is waited for)
+  DeviceGuard g(h->device);
+  if (hipDeviceSynchronize() != hipSuccess) return fail(h, LBSIM_EDEVICE, "sync failed");
+  env_rates_fill_defaults(h, nullptr);
+  const int rc = launch_check(h, "env_rates_kernel");
+  if (rc != LBSIM_OK) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(h, LBSIM_EDEVICE, "sync failed");
+  return LBSIM_OK;
+}
+
+int lbsim_get_env_rates(lbsim_t* h, float* arrival_rate_out, float* server_rate_out,
+                        void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (arrival_rate_out == nullptr && server_rate_out == nullptr) return LBSIM_OK;
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  const int rc = env_rates_ensure(h, s);
+  if (rc != LBSIM_OK) return rc;
+  const size_t B = (size_t)h->B, BS = B * h->S;
+  const EnvRates live = env_rates_live(h);
+  bool ok = true;
+  if (arrival_rate_out != nullptr)
+    ok &= hipMemcpyAsync(arrival_rate_out, live.arrival, B * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  if (server_rate_out != nullptr)
+    ok &= hipMemcpyAsync(server_rate_out, live.server, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  return ok ? LBSIM_OK : fail(h, LBSIM_EDEVICE, "per-env rates: device copy failed");
 }
 
 int lbsim_agent_obs(const float* obs, int64_t n, int S, int num_agents, int servers_per_agent,

@@ -250,12 +250,12 @@ struct GroupConst {
   int32_t dt;
   uint32_t base_ms, base_rem;
 };
-__device__ __forceinline__ GroupConst group_const(const SimParams& p, uint32_t base_ms,
-                                                  uint32_t base_rem) {
+__device__ __forceinline__ GroupConst group_const(const SimParams& p, float mean_gap,
+                                                  uint32_t base_ms, uint32_t base_rem) {
   GroupConst c;
   c.k0 = vpin(p.key0);
   c.k1 = vpin(p.key1);
-  c.mean_gap = vpin(p.mean_gap_us);
+  c.mean_gap = vpin(mean_gap);
   c.dt = vpin(p.dt_us);
   c.base_ms = vpin(base_ms);
   c.base_rem = vpin(base_rem);
@@ -605,7 +605,7 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
   // ---- 2. one arrival per iteration (as dynamics_kernel's sim_step), the group in step.  SED /
   //      SED2 scores can only be NaN when some den is 0 / inf / NaN: a wave whose servers all have
   //      finite scores runs the loop without the NaN fallbacks (a wave-uniform choice).
-  const GroupConst gc = group_const(p, base_ms, base_rem);
+  const GroupConst gc = group_const(p, env_mean_gap(st, p, b), base_ms, base_rem);
   const bool finite = lsq || alias || !V.act ||
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
@@ -691,6 +691,11 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
   V.scale = p.svc_scale[0];
 #pragma unroll
   for (int k = 1; k < G; ++k) V.scale = (k == s) ? p.svc_scale[k] : V.scale;
+  // per-env servers (lbsim_set_env_rates): one coalesced load, lane s its own server's.  An
+  // override after the shared select chain, not an if / else around it: the handles without
+  // per-env rates keep the register allocation they had (as an else branch the chain put
+  // SimParams into scratch in the 2-lane kernels)
+  if (st.env_scale != nullptr) V.scale = st.env_scale[b * (uint32_t)S + (uint32_t)(V.act ? s : 0)];
   V.den = 1.0;
   V.rcp = 1.0;
   V.score = 0.f;
@@ -708,7 +713,7 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     E.clock = 0u;
     E.dropped = 0u;
     E.arr_idx = 0u;
-    draw_arrival<1>(st, p, E, 0);
+    draw_arrival<1>(st, p, E, b, 0);
     V.cnt = 0;
     V.head_tc = 0;
     V.head = 0;

@@ -71,6 +71,7 @@ struct WaveEnv {
   int32_t next_arr;
   float next_work;
   uint32_t u2, u3;
+  float mean_gap;  // the env's mean arrival gap in us (env_mean_gap), read once at kernel entry
 };
 
 // One batch of drawn arrivals (lane j: arrival base + j) and the log of the processed ones.
@@ -125,7 +126,7 @@ __device__ __forceinline__ void wave_draw_batch(const DevState& st, const SimPar
     gap = (int32_t)st.trace_gap[r];
     wk = st.trace_work[r];
   } else {
-    gap = (int32_t)(-lb_logf(u01_open0(d.x)) * p.mean_gap_us);
+    gap = (int32_t)(-lb_logf(u01_open0(d.x)) * E.mean_gap);
     wk = -lb_logf(u01_open0(d.y));
   }
   // inclusive prefix sum over the wave by DPP: row_shr 1 / 2 / 4 / 8 within each row of 16, then
@@ -171,7 +172,8 @@ __device__ __forceinline__ void wave_flush(const SimParams& p, WaveSrv& V, WaveE
   E.dropped += (uint32_t)__builtin_popcountll(__ballot(lane < nproc && Bt.lc < 0));  // all full
   const bool ins = valid && Bt.ltc <= dt;
   uint32_t pre = 0u, rcb = 0u;
-  float scale = p.svc_scale[0];
+  // the chosen server's scale from its server lane (V.scale: the handle's or the env's own)
+  float scale = rdl(V.scale, 0);
 #pragma unroll
   for (int s = 0; s < kWaveMaxS; ++s) {
     if (s < S) {
@@ -181,7 +183,7 @@ __device__ __forceinline__ void wave_flush(const SimParams& p, WaveSrv& V, WaveE
       const uint32_t rs = rdl(V.rcnt, s);
       pre = mine ? below : pre;
       rcb = mine ? rs : rcb;
-      if (s > 0) scale = mine ? p.svc_scale[s] : scale;
+      if (s > 0) scale = mine ? rdl(V.scale, s) : scale;
       const uint32_t npush = (uint32_t)__builtin_popcountll(__ballot(valid && mine));
       const bool me = lane == s;
       V.rcnt = me ? sat_add(rs, (uint32_t)__builtin_popcountll(m)) : V.rcnt;
@@ -535,11 +537,14 @@ __device__ __forceinline__ bool dyn_wave_env(const DevState& st, const SimParams
 
   WaveEnv E;
   E.gid = p.env_id_offset + b;
+  E.mean_gap = env_mean_gap(st, p, b);
   WaveSrv V;
   V.act = lane < S;
   V.scale = p.svc_scale[0];
 #pragma unroll
   for (int k = 1; k < kWaveMaxS; ++k) V.scale = (k == lane) ? p.svc_scale[k] : V.scale;
+  // per-env servers (lbsim_set_env_rates): server lane s loads its own server's
+  if (st.env_scale != nullptr) V.scale = st.env_scale[b * (uint32_t)S + (uint32_t)(V.act ? lane : 0)];
   V.den = 1.0;
   V.rcp = 1.0;
   V.assigned = 0;
@@ -573,7 +578,7 @@ __device__ __forceinline__ bool dyn_wave_env(const DevState& st, const SimParams
         gap = (int32_t)st.trace_gap[r];
         wk = st.trace_work[r];
       } else {
-        gap = (int32_t)(-lb_logf(u01_open0(d.x)) * p.mean_gap_us);
+        gap = (int32_t)(-lb_logf(u01_open0(d.x)) * E.mean_gap);
         wk = -lb_logf(u01_open0(d.y));
       }
       E.next_arr = __builtin_amdgcn_readfirstlane(gap);

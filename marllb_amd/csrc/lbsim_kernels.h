@@ -95,6 +95,11 @@ struct DevState {
   // mean-1 work of each row
   const uint32_t* trace_gap;
   const float* trace_work;
+  // per-env workload (lbsim_set_env_rates; nullptr = the shared SimParams::mean_gap_us /
+  // svc_scale[]): env_gap[b] = the env's mean arrival gap in us, env_scale[b*S + s] = 1e6 / mu of
+  // its server s.  Read once in each dynamics kernel's prologue; not part of the snapshot.
+  const float* env_gap;
+  const float* env_scale;
 };
 
 struct SimParams {
@@ -484,11 +489,18 @@ struct FieldAliasTab {
   __device__ int32_t& operator()(int f, int k) const { return fld<MAXS>(l, F_TAB0 + f, k); }
 };
 
+// The mean arrival gap (us) of env b: its own (lbsim_set_env_rates) or the handle's shared one.
+// A wave-uniform test, made in the prologue of a step (or of a reset's first draw), never inside
+// the event loop: the value is not kept live across steps, so it costs the loops no register.
+__device__ __forceinline__ float env_mean_gap(const DevState& st, const SimParams& p, uint32_t b) {
+  return st.env_gap != nullptr ? st.env_gap[b] : p.mean_gap_us;
+}
+
 // Arrival draw for one arrival index: gap to it, its work, its two hash words.
-__device__ __forceinline__ void arrival_from_draw(const SimParams& p, const u32x4& d,
+__device__ __forceinline__ void arrival_from_draw(float mean_gap_us, const u32x4& d,
                                                   int32_t t_prev, int32_t& next_arr,
                                                   float& work, uint32_t& u2, uint32_t& u3) {
-  const int32_t gap = (int32_t)(-lb_logf(u01_open0(d.x)) * p.mean_gap_us);
+  const int32_t gap = (int32_t)(-lb_logf(u01_open0(d.x)) * mean_gap_us);
   next_arr = t_prev + gap;
   work = -lb_logf(u01_open0(d.y));
   u2 = d.z;
@@ -497,7 +509,7 @@ __device__ __forceinline__ void arrival_from_draw(const SimParams& p, const u32x
 
 template <int MAXS>
 __device__ __forceinline__ void draw_arrival(const DevState& st, const SimParams& p,
-                                             LaneState<MAXS>& L, int32_t t_prev) {
+                                             LaneState<MAXS>& L, uint32_t b, int32_t t_prev) {
   const u32x4 d = philox4x32_10(u32x4{L.arr_idx, L.gid, L.episode, kStreamArrival << 24},
                                 p.key0, p.key1);
   if (p.trace) {
@@ -507,7 +519,7 @@ __device__ __forceinline__ void draw_arrival(const DevState& st, const SimParams
     L.u2 = d.z;
     L.u3 = d.w;
   } else {
-    arrival_from_draw(p, d, t_prev, L.next_arr, L.next_work, L.u2, L.u3);
+    arrival_from_draw(env_mean_gap(st, p, b), d, t_prev, L.next_arr, L.next_work, L.u2, L.u3);
   }
 }
 
@@ -652,7 +664,8 @@ struct EvConst {
 };
 
 template <int MAXS>
-__device__ __forceinline__ EvConst<MAXS> ev_const(const SimParams& p, uint32_t base_ms,
+__device__ __forceinline__ EvConst<MAXS> ev_const(const DevState& st, const SimParams& p,
+                                                   uint32_t b, uint32_t base_ms,
                                                    uint32_t base_rem) {
   EvConst<MAXS> c;
   uint32_t k0 = p.key0, k1 = p.key1;
@@ -663,9 +676,15 @@ __device__ __forceinline__ EvConst<MAXS> ev_const(const SimParams& p, uint32_t b
     k0 += 0x9E3779B9u;
     k1 += 0xBB67AE85u;
   }
-  c.mean_gap = vpin(p.mean_gap_us);
+  c.mean_gap = vpin(env_mean_gap(st, p, b));
+  if (st.env_scale != nullptr) {  // the env's own servers (lbsim_set_env_rates)
+    const float* const my_scale = st.env_scale + (size_t)b * (size_t)p.S;
 #pragma unroll
-  for (int s = 0; s < MAXS; ++s) c.scale[s] = vpin(s < p.S ? p.svc_scale[s] : 1.0f);
+    for (int s = 0; s < MAXS; ++s) c.scale[s] = vpin(s < p.S ? my_scale[s] : 1.0f);
+  } else {
+#pragma unroll
+    for (int s = 0; s < MAXS; ++s) c.scale[s] = vpin(s < p.S ? p.svc_scale[s] : 1.0f);
+  }
   c.dt = vpin(p.dt_us);
   c.S = p.S;
   c.Q = p.Q;
@@ -1120,7 +1139,7 @@ __device__ __forceinline__ void sim_step(const DevState& st, const SimParams& p,
   // ---- 2. one arrival per iteration (3. the final pops up to dt in the last iterations).  The
   //      SED/SED2 scores can only be NaN when some den is 0 / inf / NaN: a wave whose envs all
   //      have finite scores runs the loop without the NaN fallbacks (a wave-uniform choice).
-  const EvConst<MAXS> ec = ev_const<MAXS>(p, base_ms, base_rem);
+  const EvConst<MAXS> ec = ev_const<MAXS>(st, p, b, base_ms, base_rem);
   if ((lsq || alias || __all(finite_scores)) && !p.leak && st.res_dur == nullptr)
     event_loop<MAXS, POLICY, TRACE, true>(st, p, L, l, ec, den, rcp, n_alias, my_res, my_ring);
   else
@@ -1267,7 +1286,7 @@ __global__ void __launch_bounds__(64 * kDynWaves<MAXS>)
     L.clock = 0u;
     L.dropped = 0u;
     L.arr_idx = 0u;
-    draw_arrival<MAXS>(st, p, L, 0);
+    draw_arrival<MAXS>(st, p, L, b, 0);
     trace_prefetch<MAXS>(st, p, L);
     clear_servers<MAXS>(p, L, l);
     if (p.leak)  // a new episode: no lost flows yet (n_flow_on_mode VPP)

@@ -4,6 +4,8 @@ The path shards perfectly: env b's trajectory depends only on (seed, global env 
 rank r owns global ids [r*B, (r+1)*B) through `env_id_offset` and ranks never exchange data.  The
 only collectives are around measurement: a barrier before/after the timed region and max/sum
 reductions of the per-rank results.  Weak scaling: per-rank B is fixed as world grows.
+Per-env rates (VecLoadBalanceEnv.set_rates) shard the same way: a rank passes its own rows,
+arrays[lo:hi] of the global (B,) / (B, S) arrays.
 """
 import os
 from dataclasses import dataclass

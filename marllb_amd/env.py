@@ -126,7 +126,7 @@ def make_config(num_envs: int, num_servers: int = 4, action_type: str = "discret
     their fct, at the wrap-up time (completion + flow_timeout + the wait for the next flow in the
     bucket, of mean flow_buckets / arrival_rate) and stamped with it.  0 = off.
     lost_fin_pending: the guesses each server holds until their wrap-up (a guess arriving at a
-    full ring is dropped and counted, Handle.lost_fin_overflow).
+    full ring is dropped and counted, Handle.lost_fin_overflow()).
     reservoir_mode: "algr" = problem-01's Algorithm R (reservoir.py:64-85); "vpp" = the data
     plane's rule, every sample overwrites slot rand() % 128 of a zeroed reservoir
     (lbhash.h:108,179), for feature_mode="upstream" / the VPP export.
@@ -254,6 +254,43 @@ class Handle:
         self.check(self.lib.lbsim_set_trace(self.h, ctypes.c_void_p(gap.data_ptr()),
                                             ctypes.c_void_p(work.data_ptr()), trace.rows,
                                             ctypes.c_void_p(stream)))
+
+    def _stream(self) -> int:
+        torch = _torch()
+        return torch.cuda.current_stream(torch.device("cuda", self.device_index)).cuda_stream
+
+    def set_env_rates(self, arrival=None, server=None) -> None:
+        """Per-env workload (lbsim_set_env_rates): arrival (B,) and / or server (B, S) f32
+        contiguous tensors on the handle's device, flows/s; None leaves that one as it is."""
+        self.check(self.lib.lbsim_set_env_rates(
+            self.h, ctypes.c_void_p(arrival.data_ptr() if arrival is not None else None),
+            ctypes.c_void_p(server.data_ptr() if server is not None else None),
+            ctypes.c_void_p(self._stream())))
+
+    def clear_env_rates(self) -> None:
+        """Back to the config's shared rates (lbsim_clear_env_rates)."""
+        self.check(self.lib.lbsim_clear_env_rates(self.h))
+
+    def env_rates(self):
+        """The rates in force, (arrival (B,), server (B, S)) f32 device tensors: the per-env
+        ones, or the config's for every env when none are set (lbsim_get_env_rates)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        B, S = int(self.cfg.num_envs), int(self.cfg.num_servers)
+        arrival = torch.empty(B, dtype=torch.float32, device=dev)
+        server = torch.empty((B, S), dtype=torch.float32, device=dev)
+        self.check(self.lib.lbsim_get_env_rates(self.h, ctypes.c_void_p(arrival.data_ptr()),
+                                                ctypes.c_void_p(server.data_ptr()),
+                                                ctypes.c_void_p(self._stream())))
+        return arrival, server
+
+    def lost_fin_overflow(self) -> np.ndarray:
+        """Per env (B,) uint32: the lost-FIN guesses dropped at a full pending ring this episode
+        (the snapshot's last section, lf_over); zeros on a handle without lost-FIN."""
+        B = int(self.cfg.num_envs)
+        if not self.cfg.lost_fin_prob > 0:
+            return np.zeros(B, np.uint32)
+        return np.frombuffer(self.state_bytes()[-4 * B:], dtype=np.uint32).copy()
 
 
 class VecLoadBalanceEnv:
@@ -519,6 +556,41 @@ class VecLoadBalanceEnv:
             seed = int.from_bytes(os.urandom(8), "little")
         self.handle.check(self.handle.lib.lbsim_seed(self.handle.h, int(seed) & (2**64 - 1)))
         return [seed]
+
+    def _rates_arg(self, x, shape, name):
+        """A rates argument as a contiguous f32 tensor of `shape` on the env's device (or None)."""
+        if x is None:
+            return None
+        torch = _torch()
+        t = torch.as_tensor(x)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+        return t.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def set_rates(self, arrival_rate=None, server_rates=None) -> None:
+        """Per-env workload for domain-randomised batches: arrival_rate (B,) and / or
+        server_rates (B, S) in flows/s, tensors or arrays on any device (cast to f32); None leaves
+        that one as it is.  From the next launch on (step, reset, warm-up) every env draws its
+        arrival gaps and service times from its own rates; legal before the first reset(), as
+        set_trace.  Ranges are make_config's (a value outside them: ValueError, the previous rates
+        stay in force).  arrival_rate is not supported with lost_fin_prob > 0 or a trace
+        (LbsimError, code ENOTSUP); server_rates is.  The rates are not part of get_state(); a
+        shard passes its own rows, arrays[lo:hi].  graph_mode: the first call must precede the
+        capture; later calls rewrite the same device arrays, so replays see them
+        (marllb_amd.randomize.sample_rates draws such arrays)."""
+        B, S = self.num_envs, self.num_servers
+        a = self._rates_arg(arrival_rate, (B,), "arrival_rate")
+        m = self._rates_arg(server_rates, (B, S), "server_rates")
+        self.handle.set_env_rates(a, m)
+
+    def clear_rates(self) -> None:
+        """Back to the config's shared arrival_rate / server_rates."""
+        self.handle.clear_env_rates()
+
+    @property
+    def rates(self):
+        """(arrival (B,), server (B, S)) f32 device tensors: the rates in force."""
+        return self.handle.env_rates()
 
     def get_state(self) -> bytes:
         return self.handle.state_bytes()

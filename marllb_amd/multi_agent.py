@@ -224,5 +224,16 @@ class VecMultiAgentLoadBalanceEnv:
             raise RuntimeError("call reset() before get_state()")
         return self._state
 
+    def set_rates(self, arrival_rate=None, server_rates=None) -> None:
+        """Per-env arrival (B,) / server (B, S) rates: VecLoadBalanceEnv.set_rates."""
+        self.vec.set_rates(arrival_rate, server_rates)
+
+    def clear_rates(self) -> None:
+        self.vec.clear_rates()
+
+    @property
+    def rates(self):
+        return self.vec.rates
+
     def close(self):
         self.vec.close()
