@@ -68,6 +68,7 @@ struct lbsim {
   int B, S, Q;
   DevState st;
   SimParams prm;
+  StepPlan plan;  // which kernels a step / reset launches (lbsim_plan.h): made once, at create
   std::vector<void*> allocs;
   void* trace_buf = nullptr;  // gap_us[rows] then work[rows]
   unsigned long long* stats_buf = nullptr;  // lbsim_step_stats sums (2 x u64)
@@ -481,14 +482,25 @@ std::string short_kernel_name(const char* raw) {
   return s;
 }
 
-LaunchCtx ctx(const lbsim_t* h) {
-  return LaunchCtx{h->st, h->prm, h->B, h->S, h->simds, h->cfg.dyn_mapping};
+LaunchCtx ctx(const lbsim_t* h) { return LaunchCtx{h->plan, h->st, h->prm}; }
+
+// The handle's plan: the process's overrides are read on the first call and kept.
+StepPlan plan_of(const lbsim_t* h) {
+  static const Overrides ov = Overrides::from_env();
+  const SimParams& p = h->prm;
+  PlanInput in{};
+  in.B = h->B, in.S = h->S, in.Q = p.Q, in.policy = p.policy;
+  in.trace = p.trace != 0, in.fail = p.fail_thr != 0u, in.leak = p.leak != 0;
+  in.split = p.split != 0, in.res_vpp = p.res_vpp != 0, in.dur_plane = dur_plane(p);
+  in.next_reset = p.next_reset != 0;
+  in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
+  return make_plan(in, ov);
 }
 
 int launch_dynamics(lbsim_t* h, const void* action, int dtype, int32_t* assign,
                     const uint8_t* mask, int mode, hipStream_t stream) {
   ProfScope ps(h, stream, mode == kModeStep ? 0 : 2);
-  if (mode == kModeStep && h->prm.next_reset)  // next-step auto-reset: done envs reset instead
+  if (mode == kModeStep && h->plan.nr)  // next-step auto-reset: done envs reset instead
     launch_dynamics_step_nr(ctx(h), action, dtype, assign, mask, stream);
   else if (mode == kModeStep)
     launch_dynamics_step(ctx(h), action, dtype, assign, mask, stream);
@@ -520,43 +532,6 @@ ObsOutputs obs_outputs(const lbsim_step_outputs_t* out, bool reset) {
   o.num_agents = out->num_agents;
   o.servers_per_agent = out->servers_per_agent;
   return o;
-}
-
-// The step kernel a handle asks for: its config, else LBSIM_STEP_KERNEL=split|fused, else AUTO.
-int step_kernel_of(const lbsim_t* h) {
-  static const int env = [] {
-    const char* e = std::getenv("LBSIM_STEP_KERNEL");
-    if (e != nullptr && std::strcmp(e, "split") == 0) return LBSIM_STEP_SPLIT;
-    if (e != nullptr && std::strcmp(e, "fused") == 0) return LBSIM_STEP_FUSED;
-    return LBSIM_STEP_AUTO;
-  }();
-  return h->cfg.step_kernel != LBSIM_STEP_AUTO ? h->cfg.step_kernel : env;
-}
-
-// The one-launch wave step (step_wave_kernel): one wave per env and S <= 8, FUSED asked for, or
-// AUTO on batches of at most 4 envs per SIMD, where one launch instead of two pays: 2048 x 4
-// 0.0711 -> 0.0620 ms per step, 4096 x 4 +2.5 % (profiles/r03w/ab_step_wave_fused.txt).  S = 5-8
-// between 2 and 4 envs per SIMD: the wave dynamics alone lose to the server-per-lane groups there
-// (dyn_wave_ok), the one launch with both chunks observed in it wins (profiles/r04s/).
-bool use_step_wave(const lbsim_t* h) {
-  const LaunchCtx L = ctx(h);
-  // next-step auto-reset handles step in two launches (the dynamics' kModeStepNR instantiation)
-  if (!dyn_wave_fits(L) || h->prm.next_reset) return false;
-  const int k = step_kernel_of(h);
-  if (k == LBSIM_STEP_FUSED) return dyn_wave_ok(L);
-  return k == LBSIM_STEP_AUTO && (int64_t)L.B <= 4 * (int64_t)L.simds;
-}
-
-// The fused step for this handle: its config (LBSIM_STEP_KERNEL=split|fused overrides AUTO) and
-// a group width that has a fused form.
-bool use_fused_step(const lbsim_t* h) {
-  // AUTO = SPLIT: the fused kernel measured slower at every shape tried
-  if (step_kernel_of(h) != LBSIM_STEP_FUSED || h->prm.next_reset) return false;
-  // full handles (dynamics_group_full_kernel: leak, a duration plane, lost-FIN deferral,
-  // reservoir_mode VPP) step in the two launches
-  if (h->prm.leak || dur_plane(h->prm) || h->prm.res_vpp) return false;
-  const int g = dyn_group_lanes(ctx(h));
-  return g >= 2 && g <= 16;
 }
 
 int launch_observe(lbsim_t* h, const ObsOutputs& o, const uint8_t* mask, int mode,
@@ -658,6 +633,7 @@ int lbsim_create(const lbsim_config_t* cfg, int device, lbsim_t** out) {
   h->initialised = false;
   memset(&h->st, 0, sizeof(h->st));
   derive_params(*cfg, h->prm);
+  h->plan = plan_of(h);
   for (Section& sec : sections(h)) {
     void* p = nullptr;
     if (hipMalloc(&p, sec.bytes) != hipSuccess) {
@@ -704,9 +680,7 @@ const char* lbsim_last_error(const lbsim_t* h) {
 
 int lbsim_dynamics_kernel(const lbsim_t* h) {
   if (h == nullptr) return -1;
-  const LaunchCtx L = ctx(h);
-  if (dyn_wave_ok(L)) return LBSIM_DYN_KERNEL_WAVE;
-  return dyn_group_lanes(L) == 0 ? LBSIM_DYN_KERNEL_ENV_LANE : LBSIM_DYN_KERNEL_GROUP;
+  return h->plan.dyn.kernel;
 }
 
 int lbsim_seed(lbsim_t* h, uint64_t seed) {
@@ -782,16 +756,14 @@ int lbsim_step_ex(lbsim_t* h, const void* action, int action_dtype,
   LaunchLog log(h, 0);
   const hipStream_t s = (hipStream_t)stream;
   const ObsOutputs o = obs_outputs(out, false);
-  if (use_step_wave(h)) {
+  if (h->plan.form == kStepWave) {
     ProfScope ps(h, s, 4);
     launch_step_wave(ctx(h), action, action_dtype, out->assign_count, o, s);
     return launch_check(h, "step_wave_kernel");
   }
-  if (use_fused_step(h)) {
+  if (h->plan.form == kStepGroupFused) {
     ProfScope ps(h, s, 4);
-    const LaunchCtx L = ctx(h);
-    if (!launch_fused_step(L, dyn_group_lanes(L), action, action_dtype, out->assign_count, o, s))
-      return fail(h, LBSIM_EINVAL, "no fused step for this group width");
+    launch_fused_step(ctx(h), action, action_dtype, out->assign_count, o, s);
     return launch_check(h, "fused_step_kernel");
   }
   h->prof.chain = true;  // dynamics then observe back to back on s: one event between them

@@ -33,7 +33,7 @@
 // Same event sequence, same arithmetic, same state layout as the other two
 // mappings: interchangeable between launches, bit-identical to the oracle.  S <= 8 (NG = 1, 2, 4
 // ring registers), Q <= 32 and the SED / SED2 / LSQ / LSQ2 policies (ALIAS and larger shapes use
-// the group kernel: dyn_wave_ok in lbsim_internal.h).
+// the group kernel: make_plan in lbsim_plan.h).
 #pragma once
 
 #include "lbsim_dyn_group.h"

@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(64)
   }
 }
 
-// The small-batch step (dyn_wave_fits: S <= 8, at most 4 envs per SIMD): one wave per env steps it
+// The small-batch step (kStepWave: S <= 8, at most 4 envs per SIMD): one wave per env steps it
 // (dyn_wave_env) and then observes it (observe_env_wave: one chunk for S <= 4, two for 5-8), so the
 // step is ONE launch and each env's observation runs as soon as its own event loop ends, while
 // slower envs still simulate.  Same routines, same order: the same bits as the two launches.
@@ -75,93 +75,34 @@ __global__ void __launch_bounds__(64, OCC)
   observe_env_wave<MAXS>(st, p, out, blockIdx.x, L.obs, s_obs, s_act, lane);
 }
 
-template <int NG, int POLICY, int OCC>
-void launch_wo(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
-               const ObsOutputs& o, hipStream_t s) {
-  const dim3 block(64), grid((unsigned)L.B);
-  if constexpr (NG == 4) {  // S = 5-8: both chunks
-    if (L.prm.trace)
-      LBSIM_LAUNCH((step_wave_kernel<4, POLICY, true, OCC, 8>), grid, block, 0, s, L.st, L.prm,
-                   action, dtype, assign, o);
-    else
-      LBSIM_LAUNCH((step_wave_kernel<4, POLICY, false, OCC, 8>), grid, block, 0, s, L.st, L.prm,
-                   action, dtype, assign, o);
-  } else {
-    if (L.prm.trace)
-      LBSIM_LAUNCH((step_wave_kernel<NG, POLICY, true, OCC>), grid, block, 0, s, L.st, L.prm,
-                   action, dtype, assign, o);
-    else
-      LBSIM_LAUNCH((step_wave_kernel<NG, POLICY, false, OCC>), grid, block, 0, s, L.st, L.prm,
-                   action, dtype, assign, o);
-  }
-}
-
-// OCC 2 up to 2 envs per SIMD, else 4; LBSIM_STEP_WAVE_OCC = 2 | 4 forces one form at every
-// batch size (the parity tests run the OCC-4 kernel that serves 2-4 envs per SIMD -- BASELINE
-// configs[1]'s 4096 x 4 -- on every small-batch case).
-template <int NG, int POLICY>
-void launch_w(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
-              const ObsOutputs& o, hipStream_t s) {
-  static const int forced = env_int("LBSIM_STEP_WAVE_OCC", 0);
-  const bool occ2 = forced == 2 || (forced != 4 && (int64_t)L.B <= 2 * (int64_t)L.simds);
-  if (occ2) launch_wo<NG, POLICY, 2>(L, action, dtype, assign, o, s);
-  else launch_wo<NG, POLICY, 4>(L, action, dtype, assign, o, s);
-}
-
-template <int NG>
-void launch_wpol(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
-                 const ObsOutputs& o, hipStream_t s) {
-  switch (L.prm.policy) {
-    case LBSIM_POLICY_SED: launch_w<NG, 0>(L, action, dtype, assign, o, s); break;
-    case LBSIM_POLICY_SED2: launch_w<NG, 1>(L, action, dtype, assign, o, s); break;
-    case LBSIM_POLICY_LSQ: launch_w<NG, 2>(L, action, dtype, assign, o, s); break;
-    default: launch_w<NG, 3>(L, action, dtype, assign, o, s); break;
-  }
-}
-
-template <int G, int POLICY>
-void launch_g(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
-              const ObsOutputs& o, hipStream_t s) {
-  constexpr int MAXS = G < 4 ? 4 : G;
-  const dim3 block(64), grid((unsigned)((L.B + 64 / G - 1) / (64 / G)));
-  if (L.prm.trace)
-    LBSIM_LAUNCH((fused_step_kernel<G, MAXS, POLICY, true>), grid, block, 0, s, L.st, L.prm,
-                       action, dtype, assign, o);
-  else
-    LBSIM_LAUNCH((fused_step_kernel<G, MAXS, POLICY, false>), grid, block, 0, s, L.st,
-                       L.prm, action, dtype, assign, o);
-}
-
-template <int G>
-void launch_pol(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
-                const ObsOutputs& o, hipStream_t s) {
-  switch (L.prm.policy) {
-    case LBSIM_POLICY_SED: launch_g<G, 0>(L, action, dtype, assign, o, s); break;
-    case LBSIM_POLICY_SED2: launch_g<G, 1>(L, action, dtype, assign, o, s); break;
-    case LBSIM_POLICY_LSQ: launch_g<G, 2>(L, action, dtype, assign, o, s); break;
-    case LBSIM_POLICY_LSQ2: launch_g<G, 3>(L, action, dtype, assign, o, s); break;
-    default: launch_g<G, 4>(L, action, dtype, assign, o, s); break;
-  }
-}
-
 }  // namespace
 
+// StepPlan (lbsim_plan.h) form kStepWave: width = NG, occ, obs_maxs (4, or 8 with NG = 4: S = 5-8,
+// both chunks -- the pairs that are instantiated); no ALIAS.
 void launch_step_wave(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
                       const ObsOutputs& o, hipStream_t s) {
-  if (L.S <= 2) launch_wpol<1>(L, action, dtype, assign, o, s);
-  else if (L.S <= 4) launch_wpol<2>(L, action, dtype, assign, o, s);
-  else launch_wpol<4>(L, action, dtype, assign, o, s);
+  const StepPlan& p = L.plan;
+  pick<1, 2, 4>(p.width, [&](auto N) { pick<0, 1, 2, 3>(L.prm.policy, [&](auto P) {
+    pick_bool(L.prm.trace != 0, [&](auto T) { pick<2, 4>(p.occ, [&](auto OCC) {
+      constexpr int NG = decltype(N)::value;
+      LBSIM_LAUNCH((step_wave_kernel<NG, decltype(P)::value, decltype(T)::value,
+                                     decltype(OCC)::value, (NG == 4 ? 8 : kObsChunk)>),
+                   dim3(p.grid), dim3(64), 0, s, L.st, L.prm, action, dtype, assign, o);
+    }); });
+  }); });
 }
 
-bool launch_fused_step(const LaunchCtx& L, int group_lanes, const void* action, int dtype,
-                       int32_t* assign, const ObsOutputs& o, hipStream_t s) {
-  switch (group_lanes) {
-    case 2: launch_pol<2>(L, action, dtype, assign, o, s); return true;
-    case 4: launch_pol<4>(L, action, dtype, assign, o, s); return true;
-    case 8: launch_pol<8>(L, action, dtype, assign, o, s); return true;
-    case 16: launch_pol<16>(L, action, dtype, assign, o, s); return true;
-    default: return false;  // S > 16: the two-launch step
-  }
+// Form kStepGroupFused: width = G <= 16, obs_maxs = max(G, 4); 64 / G envs per wave (dyn_epw 0).
+void launch_fused_step(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
+                       const ObsOutputs& o, hipStream_t s) {
+  const StepPlan& p = L.plan;
+  pick<2, 4, 8, 16>(p.width, [&](auto GG) { pick<0, 1, 2, 3, 4>(L.prm.policy, [&](auto P) {
+    pick_bool(L.prm.trace != 0, [&](auto T) {
+      constexpr int G = decltype(GG)::value;
+      LBSIM_LAUNCH((fused_step_kernel<G, (G < 4 ? 4 : G), decltype(P)::value, decltype(T)::value>),
+                   dim3(p.grid), dim3(64), 0, s, L.st, L.prm, action, dtype, assign, o);
+    });
+  }); });
 }
 
 }  // namespace lbk
