@@ -453,6 +453,45 @@ int lbsim_clear_env_rates(lbsim_t* h);
 int lbsim_get_env_rates(lbsim_t* h, float* arrival_rate_out, float* server_rate_out,
                         void* stream);
 
+/*
+ * Exact flow-completion-time statistics, opt-in per handle.  A handle with
+ * them on counts every flow that completes during a STEP of an env, once, with its true
+ * fct = completion - arrival in integer us (a lost-FIN handle counts the real value, not VPP's
+ * guess; duration_mode SERVICE still counts completion - arrival).  Not counted: completions
+ * inside a reset's warm-up steps (lbsim_reset, and the step that resets an env under next-step
+ * auto-reset), flows dropped at full queues, flows lost when a server fails.  Per (env, server):
+ * count (u32), sum_us (u64), max_us (u32) and hist[LBSIM_FLOW_STATS_BINS] (u32), cumulative over
+ * steps and episodes until cleared: a reset does not touch them (per-episode statistics: clear
+ * with the done mask a step returned).  Not part of the snapshot; a shard has its own rows.
+ * Bins: v = min(fct_us, 2^26 - 1); bin = v for v < 8, else with e = floor(log2 v)
+ * bin = 8 (e - 2) + ((v >> (e - 3)) & 7): lower edge (8 + bin % 8) << (bin / 8 - 1), at most 1/8
+ * of it wide; bin 191 is open-ended.
+ *
+ * lbsim_flow_stats_enable: allocates and zeroes the arrays (784 bytes per server; never moved)
+ * and makes the handle a full one: its steps run dynamics_group_full_kernel in two launches,
+ * whatever dyn_mapping / step_kernel ask for; results are unchanged.  Before the handle's first
+ * lbsim_reset (LBSIM_EINVAL after it, the handle stays as it was); a second call is a no-op.
+ * lbsim_step / lbsim_reset gain no allocation and no synchronisation.
+ * lbsim_flow_stats_get: asynchronous copies on `stream` into device buffers [B, S] /
+ * [B, S, LBSIM_FLOW_STATS_BINS]; any may be NULL.
+ * lbsim_flow_stats_quantiles: q_ppm[nq] (device, 1 <= nq <= 16) quantiles in parts per million,
+ * clamped to [1, 10^6], into out_us [B, nq] (per_server 0: an env's histograms and counts summed
+ * over its servers, the maximum over them) or [B, S, nq] (per_server 1); one kernel on `stream`,
+ * no host synchronisation.  With n the row's count, r = max(1, ceil(q_ppm n / 10^6)) and k the
+ * first bin whose cumulative count reaches r, the result is min(lower(k + 1) - 1, max_us), max_us
+ * for k = 191 and 0 for n = 0: at or above the exact nearest-rank quantile, less than 1/8 above
+ * it, exact for q = 1 and below 8 us.
+ * lbsim_flow_stats_clear: zeroes the rows of the envs with env_mask[b] != 0 (device mask, NULL =
+ * all); one kernel on `stream`, capturable.
+ * get / quantiles / clear return LBSIM_ENOTSUP on a handle without statistics. */
+#define LBSIM_FLOW_STATS_BINS 192
+int lbsim_flow_stats_enable(lbsim_t* h);
+int lbsim_flow_stats_get(lbsim_t* h, uint32_t* count, uint64_t* sum_us, uint32_t* max_us,
+                         uint32_t* hist, void* stream);
+int lbsim_flow_stats_quantiles(lbsim_t* h, const uint32_t* q_ppm, int nq, int per_server,
+                               uint32_t* out_us, void* stream);
+int lbsim_flow_stats_clear(lbsim_t* h, const uint8_t* env_mask, void* stream);
+
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/
  * alias_table.h:82-158, alias_table_build, rebuilt by lb_rl_node.c:92-111 from the weights the

@@ -172,6 +172,10 @@ _SIGNATURES = {
     "lbsim_set_env_rates": (ctypes.c_int, [_P, _P, _P, _P]),
     "lbsim_clear_env_rates": (ctypes.c_int, [_P]),
     "lbsim_get_env_rates": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lbsim_flow_stats_enable": (ctypes.c_int, [_P]),
+    "lbsim_flow_stats_get": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "lbsim_flow_stats_quantiles": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "lbsim_flow_stats_clear": (ctypes.c_int, [_P, _P, _P]),
     "lbsim_alias_tables": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P]),
     "lbsim_vose_tables": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P]),
     "lbsim_vose_sample": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, _P, ctypes.c_int64,

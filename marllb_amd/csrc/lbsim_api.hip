@@ -74,7 +74,11 @@ struct lbsim {
   unsigned long long* stats_buf = nullptr;  // lbsim_step_stats sums (2 x u64)
   // lbsim_set_env_rates: one block, allocated by the first call and never moved (EnvRates below)
   float* rates_buf = nullptr;
+  // lbsim_flow_stats_enable: one block (sum_us, hist, count, max_us), allocated once, never moved
+  void* flow_buf = nullptr;
+  FlowStats flow{};  // its arrays (null pointers: statistics off)
   bool initialised;  // a full reset has been issued
+  bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
   // (class, host stub) of the kernels the last lbsim_step_ex / lbsim_reset_ex launched
   std::vector<std::pair<int, const void*>> launched[2];
@@ -378,6 +382,76 @@ int launch_check(lbsim_t* h, const char* what) {
   return LBSIM_OK;
 }
 
+// ---- flow statistics (lbsim_flow_stats_*)
+static_assert(kFlowBins == LBSIM_FLOW_STATS_BINS && kFlowBins == 3 * 64,
+              "flow_quantiles_kernel: three bins per lane");
+
+// The block's arrays: sum_us[BS] (u64, first for its alignment), hist[BS * 192], count[BS],
+// max_us[BS]: 784 bytes per server.
+size_t flow_stats_bytes(size_t BS) { return BS * (8 + 4 * (size_t)kFlowBins + 4 + 4); }
+
+// One wave per output row (an env: its servers' rows summed, or one server).  Lane l holds bins
+// 3 l .. 3 l + 2, so the 64 lanes read a server's 768-byte row as one contiguous span; a wave-wide
+// inclusive scan of the lanes' totals gives the cumulative counts; per quantile a ballot finds the
+// first lane at or past the rank and that lane resolves the bin among its three.
+__global__ void __launch_bounds__(64)
+    flow_quantiles_kernel(const uint32_t* hist, const uint32_t* max_us, const uint32_t* q_ppm,
+                          int nq, int S, int per_server, uint32_t* out) {
+  const int lane = (int)threadIdx.x;
+  const size_t row = blockIdx.x;
+  const size_t srv0 = per_server ? row : row * (size_t)S;
+  const int ns = per_server ? 1 : S;
+  unsigned long long c0 = 0, c1 = 0, c2 = 0;  // an env's bin can pass 2^32 over 64 servers
+  uint32_t mx = 0u;
+  for (int s = 0; s < ns; ++s) {
+    const uint32_t* r = hist + (srv0 + (size_t)s) * kFlowBins + 3 * lane;
+    c0 += r[0];
+    c1 += r[1];
+    c2 += r[2];
+    const uint32_t m = max_us[srv0 + (size_t)s];  // wave-uniform
+    mx = m > mx ? m : mx;
+  }
+  const unsigned long long own = c0 + c1 + c2;
+  unsigned long long incl = own;
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long o = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += o;
+  }
+  const unsigned long long n = __shfl(incl, 63, 64);
+  for (int i = 0; i < nq; ++i) {
+    uint32_t q = q_ppm[i];
+    q = q < 1u ? 1u : (q > 1000000u ? 1000000u : q);
+    unsigned long long rank = ((unsigned long long)q * n + 999999ull) / 1000000ull;
+    rank = rank < 1ull ? 1ull : rank;
+    const unsigned long long past = __ballot(incl >= rank);  // n > 0: lane 63 at least
+    if (n == 0ull) {
+      if (lane == 0) out[row * (size_t)nq + (size_t)i] = 0u;
+    } else if (lane == __builtin_ctzll(past)) {
+      const unsigned long long before = incl - own;
+      const int k = 3 * lane + (before + c0 >= rank ? 0 : (before + c0 + c1 >= rank ? 1 : 2));
+      const uint32_t hi = k == kFlowBins - 1 ? mx : flow_bin_lower(k + 1) - 1u;
+      out[row * (size_t)nq + (size_t)i] = hi < mx ? hi : mx;
+    }
+  }
+}
+
+// Zeroes the rows of the masked envs (mask nullptr: all): one thread per histogram word, the
+// thread of a row's first word its count, sum and maximum too.
+__global__ void __launch_bounds__(256)
+    flow_clear_kernel(uint32_t* count, unsigned long long* sum, uint32_t* max_us, uint32_t* hist,
+                      int64_t n_words, int S, const uint8_t* mask) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_words) return;
+  const int64_t sb = i / kFlowBins;
+  if (mask != nullptr && mask[sb / S] == 0) return;
+  hist[i] = 0u;
+  if (i - sb * kFlowBins == 0) {
+    count[sb] = 0u;
+    sum[sb] = 0ull;
+    max_us[sb] = 0u;
+  }
+}
+
 // The config's rates into the live per-env arrays (every env the same), on stream s.
 void env_rates_fill_defaults(lbsim_t* h, hipStream_t s) {
   const float* def = env_rates_defaults(h);
@@ -482,7 +556,7 @@ std::string short_kernel_name(const char* raw) {
   return s;
 }
 
-LaunchCtx ctx(const lbsim_t* h) { return LaunchCtx{h->plan, h->st, h->prm}; }
+LaunchCtx ctx(const lbsim_t* h) { return LaunchCtx{h->plan, h->st, h->prm, h->flow}; }
 
 // The handle's plan: the process's overrides are read on the first call and kept.
 StepPlan plan_of(const lbsim_t* h) {
@@ -493,6 +567,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.trace = p.trace != 0, in.fail = p.fail_thr != 0u, in.leak = p.leak != 0;
   in.split = p.split != 0, in.res_vpp = p.res_vpp != 0, in.dur_plane = dur_plane(p);
   in.next_reset = p.next_reset != 0;
+  in.flow_stats = h->flow.hist != nullptr;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -668,6 +743,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->trace_buf) (void)hipFree(h->trace_buf);
     if (h->stats_buf) (void)hipFree(h->stats_buf);
     if (h->rates_buf) (void)hipFree(h->rates_buf);
+    if (h->flow_buf) (void)hipFree(h->flow_buf);
     for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
   }
   delete h;
@@ -712,6 +788,7 @@ int lbsim_reset_ex(lbsim_t* h, const uint8_t* env_mask, const lbsim_step_outputs
   DeviceGuard g(h->device);
   LaunchLog log(h, 1);
   const hipStream_t s = (hipStream_t)stream;
+  h->reset_seen = true;
   int rc = launch_dynamics(h, nullptr, 0, nullptr, env_mask, kModeReset, s);
   if (rc != LBSIM_OK) return rc;
   const ObsOutputs o = obs_outputs(out, true);
@@ -927,6 +1004,78 @@ int lbsim_get_env_rates(lbsim_t* h, float* arrival_rate_out, float* server_rate_
   if (server_rate_out != nullptr)
     ok &= hipMemcpyAsync(server_rate_out, live.server, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
   return ok ? LBSIM_OK : fail(h, LBSIM_EDEVICE, "per-env rates: device copy failed");
+}
+
+int lbsim_flow_stats_enable(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->flow_buf != nullptr) return LBSIM_OK;
+  if (h->reset_seen)
+    return fail(h, LBSIM_EINVAL, "lbsim_flow_stats_enable must precede the handle's first "
+                                 "lbsim_reset (the statistics change which kernels it launches)");
+  DeviceGuard g(h->device);
+  const size_t BS = (size_t)h->B * h->S, bytes = flow_stats_bytes(BS);
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", bytes);
+  if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(p);
+    return fail(h, LBSIM_EDEVICE, "flow statistics: hipMemset failed");
+  }
+  h->flow_buf = p;
+  h->flow.sum = (unsigned long long*)p;
+  h->flow.hist = (uint32_t*)(h->flow.sum + BS);
+  h->flow.count = h->flow.hist + BS * kFlowBins;
+  h->flow.max_us = h->flow.count + BS;
+  h->plan = plan_of(h);  // a statistics handle is a full handle (make_plan)
+  return LBSIM_OK;
+}
+
+int lbsim_flow_stats_get(lbsim_t* h, uint32_t* count, uint64_t* sum_us, uint32_t* max_us,
+                         uint32_t* hist, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->flow_buf == nullptr)
+    return fail(h, LBSIM_ENOTSUP, "flow statistics are off: call lbsim_flow_stats_enable first");
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t BS = (size_t)h->B * h->S;
+  const FlowStats& f = h->flow;
+  bool ok = true;
+  if (count != nullptr)
+    ok &= hipMemcpyAsync(count, f.count, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  if (sum_us != nullptr)
+    ok &= hipMemcpyAsync(sum_us, f.sum, BS * 8, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  if (max_us != nullptr)
+    ok &= hipMemcpyAsync(max_us, f.max_us, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  if (hist != nullptr)
+    ok &= hipMemcpyAsync(hist, f.hist, BS * kFlowBins * 4, hipMemcpyDeviceToDevice, s) ==
+          hipSuccess;
+  return ok ? LBSIM_OK : fail(h, LBSIM_EDEVICE, "flow statistics: device copy failed");
+}
+
+int lbsim_flow_stats_quantiles(lbsim_t* h, const uint32_t* q_ppm, int nq, int per_server,
+                               uint32_t* out_us, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->flow_buf == nullptr)
+    return fail(h, LBSIM_ENOTSUP, "flow statistics are off: call lbsim_flow_stats_enable first");
+  if (q_ppm == nullptr || out_us == nullptr || nq < 1 || nq > 16)
+    return fail(h, LBSIM_EINVAL, "flow quantiles: need device q_ppm / out_us and 1 <= nq <= 16 "
+                                 "(got %d)", nq);
+  DeviceGuard g(h->device);
+  const size_t rows = per_server ? (size_t)h->B * h->S : (size_t)h->B;
+  hipLaunchKernelGGL(flow_quantiles_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream,
+                     h->flow.hist, h->flow.max_us, q_ppm, nq, h->S, per_server ? 1 : 0, out_us);
+  return launch_check(h, "flow_quantiles_kernel");
+}
+
+int lbsim_flow_stats_clear(lbsim_t* h, const uint8_t* env_mask, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->flow_buf == nullptr)
+    return fail(h, LBSIM_ENOTSUP, "flow statistics are off: call lbsim_flow_stats_enable first");
+  DeviceGuard g(h->device);
+  const int64_t n = (int64_t)h->B * h->S * kFlowBins;
+  hipLaunchKernelGGL(flow_clear_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, h->flow.count, h->flow.sum, h->flow.max_us,
+                     h->flow.hist, n, h->S, env_mask);
+  return launch_check(h, "flow_clear_kernel");
 }
 
 int lbsim_agent_obs(const float* obs, int64_t n, int S, int num_agents, int servers_per_agent,
@@ -1280,6 +1429,7 @@ int lbsim_set_state(lbsim_t* h, const void* host_buf, size_t bytes) {
     src += s.bytes;
   }
   h->initialised = true;
+  h->reset_seen = true;
   return LBSIM_OK;
 }
 

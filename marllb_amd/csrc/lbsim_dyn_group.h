@@ -133,7 +133,23 @@ struct SrvLane {
   uint32_t rcnt_d;
   int32_t phead, pcnt;
   uint32_t pdue, over;
+  // flow statistics (full handles, FlowStats::hist): the server's histogram row, nullptr while
+  // this lane does not count (statistics off, no server, a reset's warm-up), and its running
+  // count / sum / maximum, stored back with the server's other words
+  uint32_t* fs_row;
+  uint32_t fs_cnt, fs_max;
+  unsigned long long fs_sum;
 };
+
+// One completed flow of fct us into the lane's flow statistics.  The histogram word is a plain
+// read-modify-write: the lane owns its server's row for the whole launch.
+__device__ __forceinline__ void flow_stats_add(SrvLane& V, uint32_t fct) {
+  if (V.fs_row == nullptr) return;
+  V.fs_cnt += 1u;
+  V.fs_sum += fct;
+  V.fs_max = fct > V.fs_max ? fct : V.fs_max;
+  V.fs_row[flow_bin(fct)] += 1u;
+}
 
 // ALIAS table of the group in LDS: word f of active position k at [f][gbase + k].  Every lane of
 // the group builds the same table (same values to the same words).
@@ -270,14 +286,14 @@ __device__ __forceinline__ GroupConst group_const(const SimParams& p, float mean
 // (profiles/r06i/) -- the plain kernel shed the full handles' code, so the hoisted keys fit.
 // FULL: the handle's features beyond the plain simulator -- n_flow_on_mode VPP's lost-flow counts,
 // a duration plane (duration_mode SERVICE), lost-FIN deferral (split reservoirs), reservoir_mode
-// VPP -- compiled only into dynamics_group_full_kernel, so none of their registers weigh on the
+// VPP, exact flow statistics (fs_on) -- compiled only into dynamics_group_full_kernel, so none of their registers weigh on the
 // plain kernel (126 VGPRs, 4 waves per SIMD; with them inlined it took 164).
 template <int G, int POLICY, bool TRACE, bool FAST, bool FULL = false>
 __device__ __forceinline__ void group_event_loop(const DevState& st, const SimParams& p,
                                                  LaneState<1>& E, SrvLane& V, int s, int gbase,
                                                  int n_alias, const GroupConst& gc, int2* win,
                                                  int32_t* atab, int4* acache, uint2* const my_res,
-                                                 int2* const my_ring) {
+                                                 int2* const my_ring, bool fs_on = false) {
   constexpr int WL = kGroupWL;
   constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
   constexpr bool alias = POLICY == kPolicyAlias;
@@ -434,6 +450,8 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
     const int slot = (FULL && p.res_vpp) ? (int)(E.u3 >> 25) : reservoir_slot_r32(V.rcnt, E.u3);
     bool split = false;  // split handles (lost-FIN): their own inserts (split_complete)
     if constexpr (FULL) {
+      // flow statistics: the true tc - ta, before a lost-FIN flow turns into its guess
+      if (fs_on && ins) flow_stats_add(V, (uint32_t)(tc_a - ta));
       split = p.split != 0;
       if (split && ins) {
         const uint64_t base_us = (uint64_t)gc.base_ms * 1000u + gc.base_rem;
@@ -489,7 +507,8 @@ template <int G, int POLICY, bool TRACE, bool FULL = false>
 __device__ __forceinline__ void sim_step_group(const DevState& st, const SimParams& p,
                                                LaneState<1>& E, SrvLane& V, uint32_t b, int s,
                                                int gbase, float w_own, const float (&wall)[G],
-                                               int2* win, int32_t* atab, int4* acache) {
+                                               int2* win, int32_t* atab, int4* acache,
+                                               bool fs_on = false) {
   constexpr int WL = kGroupWL;
   const int S = p.S, Q = p.Q;
   const int32_t dt = p.dt_us;
@@ -552,6 +571,9 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
     int32_t prev = V.last;
     uint32_t rc = V.rcnt;
     auto insert = [&](int32_t etc, int32_t eta) {
+      if constexpr (FULL) {  // flow statistics: the true tc - ta, lost-FIN or not
+        if (fs_on) flow_stats_add(V, (uint32_t)(etc - eta));
+      }
       if (FULL && p.split) {  // lost-FIN: split reservoirs and deferred guesses (split_complete)
         split_complete(st, p, V, sb, E.gid, E.episode, s, etc, eta,
                        dur_sample(p, etc, eta, eta > prev ? eta : prev),
@@ -610,7 +632,7 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
     group_event_loop<G, POLICY, TRACE, false, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                                    acache, my_res, my_ring);
+                                                    acache, my_res, my_ring, fs_on);
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
   } else if (__all(finite)) {
@@ -662,7 +684,8 @@ template <int G, int MODE, int POLICY, bool TRACE, bool FULL = false>
 __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimParams& p,
                                                const void* action, int action_dtype,
                                                int32_t* assign_out, const uint8_t* reset_mask,
-                                               uint32_t wave, int lane, DynGroupLds<POLICY>& L) {
+                                               uint32_t wave, int lane, DynGroupLds<POLICY>& L,
+                                               const FlowStats& fs = FlowStats{}) {
   static_assert(G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64,
                 "group = a power of two lanes of the wave");
   constexpr int WL = kGroupWL;
@@ -704,9 +727,14 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
 #pragma unroll
   for (int w = 0; w < 4; ++w) chgw[w * 64 + lane] = 0u;
   V.chgw = chgw + lane;
+  V.fs_row = nullptr;  // flow statistics: only load_in turns them on (a reset's warm-up is not
+  V.fs_cnt = 0u;       // the policy's doing)
+  V.fs_max = 0u;
+  V.fs_sum = 0ull;
   const uint32_t sb = b * (uint32_t)S + (uint32_t)s;
   float wall[G];
   float w_own = 1.0f;
+  const bool fs_on = FULL && fs.hist != nullptr;  // wave-uniform: the kernel's argument
 
   auto reset_in = [&]() {  // a new episode (env.py:186-213): its first arrival, empty servers
     E.episode = st.episode[b] + 1u;
@@ -774,6 +802,12 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
         V.pcnt = (int32_t)(ph >> 16);
         if (V.pcnt > 0) V.pdue = st.pend[(size_t)sb * (uint32_t)p.pend_P + (uint32_t)V.phead].x;
       }
+      if (fs.hist != nullptr) {  // flow statistics: this step's completions count
+        V.fs_row = fs.hist + (size_t)sb * kFlowBins;
+        V.fs_cnt = fs.count[sb];
+        V.fs_max = fs.max_us[sb];
+        V.fs_sum = fs.sum[sb];
+      }
     }
     if (st.down != nullptr && V.act && st.down[sb] != 0u) V.qcap = 0;  // (fail_prob handles)
     const int head = V.act ? (int)(hc & kHcHead) : 0;
@@ -827,12 +861,12 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
   if constexpr (MODE == kModeStep) {
     load_in();
     sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w_own, wall, win, atab,
-                                           acache);
+                                           acache, fs_on);
   } else if constexpr (MODE == kModeReset) {
     reset_in();
     for (int k = 0; k < p.warmup_steps; ++k)
       sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, 1.0f, wall, win, atab,
-                                             acache);
+                                             acache, fs_on);
     reset_out(0);
   } else {
     // kModeStepNR (next-step auto-reset): an env whose last step returned done resets in place of
@@ -848,7 +882,7 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     const float w = rs ? 1.0f : w_own;
     for (int k = 0; k < nsteps; ++k)
       sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w, wall, win, atab,
-                                             acache);
+                                             acache, fs_on);
     if (rs) reset_out(-1);
   }
 
@@ -876,6 +910,11 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     st.res_count[sb] = V.rcnt;
     if (st.down != nullptr) st.down[sb] = V.qcap == 0 ? 1u : 0u;
     if (FULL && p.leak) st.lost_on[sb] = (uint32_t)V.lost;
+    if (FULL && V.fs_row != nullptr) {
+      fs.count[sb] = V.fs_cnt;
+      fs.max_us[sb] = V.fs_max;
+      fs.sum[sb] = V.fs_sum;
+    }
     *reinterpret_cast<uint4*>(st.chg + (size_t)sb * 4) =
         make_uint4(chgw[lane], chgw[64 + lane], chgw[128 + lane], chgw[192 + lane]);
     if (MODE != kModeReset && assign_out != nullptr) assign_out[sb] = V.assigned;  // 0 if reset
@@ -909,15 +948,15 @@ __global__ void __launch_bounds__(64, WAVES)
 }
 
 // The same for a full handle (group_event_loop's FULL: n_flow_on_mode VPP, a duration plane,
-// lost-FIN deferral, reservoir_mode VPP): the general event loop with every feature, on its own
-// register budget.
+// lost-FIN deferral, reservoir_mode VPP, flow statistics): the general event loop with every
+// feature, on its own register budget.  fs: the flow statistics' arrays (null pointers: off).
 template <int G, int MODE, int POLICY, bool TRACE>
 __global__ void __launch_bounds__(64)
     dynamics_group_full_kernel(DevState st, SimParams p, const void* action, int action_dtype,
-                               int32_t* assign_out, const uint8_t* reset_mask) {
+                               int32_t* assign_out, const uint8_t* reset_mask, FlowStats fs) {
   __shared__ DynGroupLds<POLICY> L;
   dyn_group_wave<G, MODE, POLICY, TRACE, true>(st, p, action, action_dtype, assign_out,
-                                               reset_mask, blockIdx.x, (int)threadIdx.x, L);
+                                               reset_mask, blockIdx.x, (int)threadIdx.x, L, fs);
 }
 
 }  // namespace lbk

@@ -47,6 +47,7 @@ struct LaunchCtx {
   const StepPlan& plan;
   const DevState& st;
   const SimParams& prm;
+  const FlowStats& flow;  // the full group dynamics' flow statistics (null pointers: off)
 };
 
 // Runtime value -> template argument: pick<2, 4, 8>(v, f) calls f(std::integral_constant<int, v>)

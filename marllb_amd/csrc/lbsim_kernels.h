@@ -102,6 +102,35 @@ struct DevState {
   const float* env_scale;
 };
 
+// Exact flow statistics (lbsim_flow_stats_enable; nullptr = off), cumulative over
+// the steps since they were last cleared, per server [B*S]: completed flows, the sum and the
+// maximum of their tc - ta in us, and hist[(b*S + s)*kFlowBins + flow_bin(us)].  Written by
+// dynamics_group_full_kernel alone, each row by the lane that owns the server; a reset leaves them
+// alone, and they are not part of the snapshot.  An argument of that kernel only, not a part of
+// DevState: four more pointers there move SimParams in every kernel's argument segment, and the
+// default step's observe_pair_kernel then spilled one more VGPR.
+struct FlowStats {
+  uint32_t* count;
+  unsigned long long* sum;
+  uint32_t* max_us;
+  uint32_t* hist;
+};
+
+// The histogram of the flow statistics: 8 bins of 1 us, then 8 bins per octave up to 2^26 us (a
+// bin is at most 1/8 of its lower edge wide; the last one is open-ended).  marllb_amd/flowstats.py
+// states the same rule on the host.
+constexpr int kFlowBins = 192;  // LBSIM_FLOW_STATS_BINS
+__device__ __forceinline__ int flow_bin(uint32_t us) {
+  const uint32_t v = us < (1u << 26) ? us : (1u << 26) - 1u;
+  if (v < 8u) return (int)v;
+  const int e = 31 - __builtin_clz(v);
+  return 8 * (e - 2) + (int)((v >> (e - 3)) & 7u);
+}
+// lower edge of bin k (k = kFlowBins: the clamp, 2^26)
+__device__ __forceinline__ uint32_t flow_bin_lower(int k) {
+  return k < 8 ? (uint32_t)k : (8u + ((uint32_t)k & 7u)) << (k / 8 - 1);
+}
+
 struct SimParams {
   int32_t B, S, Q;
   int32_t dt_us;

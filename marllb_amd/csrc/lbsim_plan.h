@@ -56,6 +56,7 @@ struct PlanInput {
   int dyn_mapping;  // lbsim_dyn_mapping
   int step_kernel;  // lbsim_step_kernel
   int simds;        // SIMDs of the device (CUs x 4)
+  bool flow_stats;  // exact flow statistics are on (lbsim_flow_stats_enable)
 };
 
 enum StepForm { kStepWave, kStepGroupFused, kStepTwoLaunch };
@@ -108,10 +109,14 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
   // mapping.  Server failures and n_flow_on_mode VPP's lost-flow counts run the group / env-lane
   // kernels; lost-FIN deferral and reservoir_mode VPP the group kernel.  LBSIM_DYN_WAVE = 0
   // disables the wave kernel, and so does LBSIM_DYN_GROUP_LANES, whatever its value.
+  // Flow statistics are accumulated by the lane that owns a server for the whole launch (no
+  // atomics, bitwise reproducible): only the server-per-lane kernel's full form has that code, so
+  // a statistics handle plans exactly as a reservoir_mode VPP one does.
+  const bool full_only = in.res_vpp || in.flow_stats;
   const bool wave_fits = ov.dyn_wave != 0 && !ov.group_lanes_set &&
                          in.dyn_mapping != LBSIM_DYN_ENV_PER_LANE && S <= 8 && in.Q <= 32 &&
                          in.policy != LBSIM_POLICY_ALIAS && !in.fail && !in.leak && !in.split &&
-                         !in.res_vpp;
+                         !full_only;
   // ... and a batch small enough that one env's event-loop chain, not issue throughput, sets the
   // step time: at most 4 waves (envs) per SIMD for S <= 4 (B <= 4096 on 256 CUs), 2 for S <= 8.
   // Measured dynamics, wave vs server-per-lane groups (profiles/r03w/wave_sweep*.txt): S = 4 1024
@@ -136,13 +141,14 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
   // envs on.
   const int fl = ov.group_lanes;
   int g = 8;
-  if (in.dyn_mapping == LBSIM_DYN_ENV_PER_LANE && S <= 16 && !in.split && !in.res_vpp) g = 0;
+  if (in.dyn_mapping == LBSIM_DYN_ENV_PER_LANE && S <= 16 && !in.split && !full_only) g = 0;
   else if (fl >= S && (fl == 4 || fl == 8 || fl == 16 || fl == 32 || fl == 64)) g = fl;
   else if (S <= 2) g = 2;
   else if (S <= 4) g = B * 4 / 64 <= in.simds / 2 ? 8 : 4;
   else while (g < S) g <<= 1;
-  // a full handle (n_flow_on_mode VPP, a duration plane, lost-FIN deferral, reservoir_mode VPP)
-  const bool full = in.leak || in.dur_plane || in.res_vpp;
+  // a full handle (n_flow_on_mode VPP, a duration plane, lost-FIN deferral, reservoir_mode VPP,
+  // flow statistics)
+  const bool full = in.leak || in.dur_plane || full_only;
 
   const auto dynamics = [&](bool step) {
     DynPlan d{};

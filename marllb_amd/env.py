@@ -23,7 +23,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import _lib
+from . import _lib, flowstats
 from .spaces import Box, MultiDiscrete
 
 # the single-env facade's step polls its completion word for at most this long before a stream
@@ -284,6 +284,48 @@ class Handle:
                                                 ctypes.c_void_p(self._stream())))
         return arrival, server
 
+    def enable_flow_stats(self) -> None:
+        """Exact per-(env, server) flow statistics from now on (lbsim_flow_stats_enable): before
+        the handle's first reset (ValueError after it); a second call is a no-op."""
+        self.check(self.lib.lbsim_flow_stats_enable(self.h))
+
+    def flow_stats(self, hist: bool = False):
+        """(count (B, S) int32, sum_us (B, S) int64, max_us (B, S) int32[, hist (B, S, 192) int32])
+        device tensors holding the handle's unsigned words (lbsim_flow_stats_get), copied on the
+        current stream."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        B, S = int(self.cfg.num_envs), int(self.cfg.num_servers)
+        count = torch.empty((B, S), dtype=torch.int32, device=dev)
+        sum_us = torch.empty((B, S), dtype=torch.int64, device=dev)
+        max_us = torch.empty((B, S), dtype=torch.int32, device=dev)
+        h = torch.empty((B, S, flowstats.NBINS), dtype=torch.int32, device=dev) if hist else None
+        self.check(self.lib.lbsim_flow_stats_get(
+            self.h, ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(sum_us.data_ptr()),
+            ctypes.c_void_p(max_us.data_ptr()),
+            ctypes.c_void_p(h.data_ptr() if hist else None), ctypes.c_void_p(self._stream())))
+        return (count, sum_us, max_us, h) if hist else (count, sum_us, max_us)
+
+    def flow_quantiles(self, q_ppm, per_server: bool = False):
+        """Quantiles in us, (B, nq) or (B, S, nq) int32 device tensor, of q_ppm: 1 to 16 integers
+        in parts per million (a list, or an int32 device tensor); lbsim_flow_stats_quantiles."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        q = torch.as_tensor(q_ppm).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        B, S, nq = int(self.cfg.num_envs), int(self.cfg.num_servers), int(q.numel())
+        out = torch.empty((B, S, nq) if per_server else (B, nq), dtype=torch.int32, device=dev)
+        self.check(self.lib.lbsim_flow_stats_quantiles(
+            self.h, ctypes.c_void_p(q.data_ptr() if nq else None), nq, 1 if per_server else 0,
+            ctypes.c_void_p(out.data_ptr() if nq else None), ctypes.c_void_p(self._stream())))
+        return out
+
+    def clear_flow_stats(self, mask=None) -> None:
+        """Zero the statistics of the envs with mask[b] set (a contiguous uint8 device tensor of B
+        entries; None: every env); lbsim_flow_stats_clear, one kernel on the current stream."""
+        self.check(self.lib.lbsim_flow_stats_clear(
+            self.h, ctypes.c_void_p(mask.data_ptr() if mask is not None else None),
+            ctypes.c_void_p(self._stream())))
+
     def lost_fin_overflow(self) -> np.ndarray:
         """Per env (B,) uint32: the lost-FIN guesses dropped at a full pending ring this episode
         (the snapshot's last section, lf_over); zeros on a handle without lost-FIN."""
@@ -314,12 +356,20 @@ class VecLoadBalanceEnv:
     replayable: every output is a buffer allocated once and rewritten by each step (callers that
     keep a step's outputs must copy them), and the masked auto-reset launch runs every step (it
     leaves envs that are not done untouched) instead of being skipped on a host-side count.
+    flow_stats=True keeps exact statistics of the true flow completion times on the device, per
+    (env, server): every flow that completes in a step counts once (warm-up steps of a reset,
+    dropped flows and flows lost to a server failure do not), cumulative across steps and
+    episodes until clear_flow_stats (per-episode statistics: clear_flow_stats(done)).  Read them
+    with flow_stats() and fct_quantiles().  Such an env steps through the full server-per-lane
+    dynamics kernel whatever dyn_mapping / step_kernel say; its results are unchanged
+    (DESIGN.md §3.11).
     """
 
     def __init__(self, num_envs: int, num_servers: int = 4, *, device=None,
                  autoreset: bool = True, keep_terminal_obs: bool = False,
                  strict_actions: bool = False, feature_mode: str = "problem01",
-                 graph_mode: bool = False, autoreset_mode: str = "same_step", **kwargs):
+                 graph_mode: bool = False, autoreset_mode: str = "same_step",
+                 flow_stats: bool = False, **kwargs):
         torch = _torch()
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError(f"Unknown autoreset_mode: {autoreset_mode}")
@@ -353,6 +403,8 @@ class VecLoadBalanceEnv:
         self.keep_terminal_obs = keep_terminal_obs
         self.strict_actions = strict_actions
         self.handle = Handle(self.cfg, self.device_index)
+        if flow_stats:
+            self.handle.enable_flow_stats()
         if self.trace is not None:
             self.handle.set_trace(self.trace)
         self._reset_done = False
@@ -591,6 +643,43 @@ class VecLoadBalanceEnv:
     def rates(self):
         """(arrival (B,), server (B, S)) f32 device tensors: the rates in force."""
         return self.handle.env_rates()
+
+    def flow_stats(self, per_server: bool = False, hist: bool = False) -> Dict[str, Any]:
+        """The exact flow statistics since the last clear, as device tensors of shape (B,) or,
+        per_server, (B, S): count (int64), mean_s (f64, sum_us / count * 1e-6, 0 where no flow
+        completed), max_s (f64), sum_us (int64) and, with hist=True, hist (..., 192) int64 (bins:
+        marllb_amd.flowstats).  An env's row sums its servers (max_s: their maximum).  Needs
+        flow_stats=True at construction (LbsimError ENOTSUP otherwise).  No host synchronisation."""
+        torch = _torch()
+        got = self.handle.flow_stats(hist=hist)
+        count = got[0].to(torch.int64) & 0xFFFFFFFF  # the handle's words are unsigned
+        sum_us = got[1]
+        max_us = got[2].to(torch.int64) & 0xFFFFFFFF
+        h = got[3].to(torch.int64) & 0xFFFFFFFF if hist else None
+        if not per_server:
+            count, sum_us, max_us = count.sum(1), sum_us.sum(1), max_us.max(1).values
+            h = h.sum(1) if hist else None
+        mean = torch.where(count > 0, sum_us.double() / count.clamp(min=1).double() * 1e-6,
+                           torch.zeros((), dtype=torch.float64, device=self.device))
+        out = {"count": count, "mean_s": mean, "max_s": max_us.double() * 1e-6, "sum_us": sum_us}
+        if hist:
+            out["hist"] = h
+        return out
+
+    def fct_quantiles(self, q=(0.5, 0.9, 0.99), per_server: bool = False):
+        """Quantiles of the true flow completion time in seconds, f32 (B, nq) or, per_server,
+        (B, S, nq), read off the histograms by one kernel: at or above the exact nearest-rank
+        quantile and less than 1/8 above it (exact at q = 1); 0 where no flow completed.  q: 1 to
+        16 fractions in (0, 1], taken to the nearest part per million."""
+        torch = _torch()
+        q_ppm = [int(round(float(x) * flowstats.PPM)) for x in np.atleast_1d(q).tolist()]
+        us = self.handle.flow_quantiles(q_ppm, per_server)
+        return ((us.to(torch.int64) & 0xFFFFFFFF).double() * 1e-6).float()
+
+    def clear_flow_stats(self, mask=None) -> None:
+        """Zero the flow statistics of every env (mask None) or of those with mask[b] true: any
+        bool / uint8 tensor of num_envs entries, e.g. the done a step returned."""
+        self.handle.clear_flow_stats(None if mask is None else self._mask(mask))
 
     def get_state(self) -> bytes:
         return self.handle.state_bytes()
@@ -937,6 +1026,26 @@ class LoadBalanceEnv:
         if done:
             info["episode"] = {"r": self.episode_return, "l": self.current_step}
         return next_obs, reward, done, info
+
+    # ---- exact flow statistics (LoadBalanceEnv(flow_stats=True); VecLoadBalanceEnv.flow_stats)
+    def _flow_vec(self) -> "VecLoadBalanceEnv":
+        if self._vec is None:
+            raise RuntimeError("flow statistics need the GPU simulator (not reference_plumbing)")
+        return self._vec
+
+    def flow_stats(self, per_server: bool = False, hist: bool = False) -> Dict[str, Any]:
+        """The env's exact flow statistics as Python scalars (per_server: lists of num_servers
+        entries): count, mean_s, max_s, sum_us and, with hist=True, the 192-bin histogram."""
+        st = self._flow_vec().flow_stats(per_server=per_server, hist=hist)
+        return {k: v[0].cpu().tolist() for k, v in st.items()}
+
+    def fct_quantiles(self, q=(0.5, 0.9, 0.99), per_server: bool = False) -> list:
+        """Flow completion time quantiles in seconds: a list of len(q) floats (per_server: one
+        such list per server)."""
+        return self._flow_vec().fct_quantiles(q, per_server)[0].cpu().tolist()
+
+    def clear_flow_stats(self) -> None:
+        self._flow_vec().clear_flow_stats()
 
     def render(self, mode: str = "human"):
         if mode == "human":

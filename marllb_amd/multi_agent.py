@@ -235,5 +235,15 @@ class VecMultiAgentLoadBalanceEnv:
     def rates(self):
         return self.vec.rates
 
+    def flow_stats(self, per_server: bool = False, hist: bool = False):
+        """Exact flow statistics of an env made with flow_stats=True: VecLoadBalanceEnv.flow_stats."""
+        return self.vec.flow_stats(per_server, hist)
+
+    def fct_quantiles(self, q=(0.5, 0.9, 0.99), per_server: bool = False):
+        return self.vec.fct_quantiles(q, per_server)
+
+    def clear_flow_stats(self, mask=None) -> None:
+        self.vec.clear_flow_stats(mask)
+
     def close(self):
         self.vec.close()
