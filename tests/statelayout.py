@@ -65,6 +65,14 @@ def parse(buf: bytes, B, S, Q, normalize, failures=False, leak=False, dur_plane=
     return d
 
 
+def parse_cfg(buf: bytes, cfg, B=None):
+    """parse with every flag taken from the handle's LbsimConfig.  B: the envs in the snapshot,
+    where that is not cfg.num_envs (a one-env snapshot of a sharded reference)."""
+    return parse(buf, cfg.num_envs if B is None else B, cfg.num_servers, cfg.queue_capacity,
+                 bool(cfg.normalize_obs), cfg.fail_prob > 0, has_leak(cfg), has_dur_plane(cfg),
+                 split_p(cfg))
+
+
 def live_pend(d, B, S, P):
     """Pending guesses in their rings (entries past the count are not state), by position from
     the head."""

@@ -24,8 +24,7 @@ def _run(oracle_mod, B, S, steps, seed=5, **kw):
     out = []
     for _ in range(steps):
         out.append(ora.step(rng.integers(0, 3, (B, S)).astype(np.int64)))
-    st = statelayout.parse(ora.state_bytes(), B, S, cfg.queue_capacity, False, cfg.fail_prob > 0,
-                           statelayout.has_leak(cfg), split_P=statelayout.split_p(cfg))
+    st = statelayout.parse_cfg(ora.state_bytes(), cfg)
     ora.close()
     return st, out
 
@@ -52,8 +51,7 @@ def _run_split(oracle_mod, B, S, steps, seed=5, **kw):
     states = []
     for _ in range(steps):
         ora.step(rng.integers(0, 3, (B, S)).astype(np.int64))
-        states.append(statelayout.parse(ora.state_bytes(), B, S, cfg.queue_capacity, False,
-                                        split_P=statelayout.split_p(cfg)))
+        states.append(statelayout.parse_cfg(ora.state_bytes(), cfg))
     ora.close()
     return cfg, states
 
@@ -142,7 +140,7 @@ def test_server_failures(oracle_mod):
     dropped_prev = 0
     for k in range(steps):
         obs, rew, done, assign = ora.step(rng.integers(0, 3, (B, S)).astype(np.int64))
-        st = statelayout.parse(ora.state_bytes(), B, S, cfg.queue_capacity, False, True)
+        st = statelayout.parse_cfg(ora.state_bytes(), cfg)
         down = st["down"].reshape(B, S).astype(bool)
         assert (obs[down] == 0).all(), "a down server's row is all zeros"
         assert (assign[down] == 0).all(), "a down server takes no flows"
@@ -315,9 +313,7 @@ def test_n_flow_on_vpp_counts_lost_flows(oracle_mod):
         ora.reset()
         rng = np.random.default_rng(5)
         outs[mode] = [ora.step(rng.integers(0, 3, (B, S)).astype(np.int64)) for _ in range(steps)]
-        outs[mode + "_st"] = statelayout.parse(ora.state_bytes(), B, S, cfg.queue_capacity, False,
-                                               False, statelayout.has_leak(cfg),
-                                               split_P=statelayout.split_p(cfg))
+        outs[mode + "_st"] = statelayout.parse_cfg(ora.state_bytes(), cfg)
         ora.close()
     st_q, st_v = outs["queue_st"], outs["vpp_st"]
     # the leaky count steers the assignments, so the two runs differ ...

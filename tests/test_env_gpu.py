@@ -5,13 +5,9 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from tests.parity import need_gpu  # noqa: E402, F401  (the autouse device guard)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test run without a HIP device")
 
 
 def make(**kw):

@@ -4,27 +4,14 @@ The RNG is keyed by global env id, so one GPU handle of B heterogeneous envs mus
 oracle handles (env_id_offset = b), each created with that env's own rates: every comparison here
 is bit for bit, observations, rewards, done flags, assignment counts and the device state.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from tests import statelayout
+from tests import parity, statelayout
+from tests.parity import ENV_LANE, GROUP, WAVE, actions, compare_state, lib, step_both  # noqa: F401
 
 torch = pytest.importorskip("torch")
 gpu = pytest.mark.gpu
-
-ENV_LANE, GROUP, WAVE = 0, 1, 2  # lbsim_dyn_kernel
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test run without a HIP device")
-    from marllb_amd import _lib
-    return _lib
 
 
 def make_rates(B, S, seed):
@@ -78,7 +65,8 @@ class PerEnvOracles:
         res = [o.step(a[b:b + 1]) for b, o in enumerate(self.envs)]
         return tuple(np.concatenate([x[i] for x in res]) for i in range(4))
 
-    def states(self):
+    def state_bytes(self):
+        """One-env snapshots in env order (parity.compare_state stacks them)."""
         return [o.state_bytes() for o in self.envs]
 
     def with_rates(self, oracle_mod, kw, r, mu, offset=0):
@@ -93,109 +81,45 @@ class PerEnvOracles:
             o.close()
 
 
-def stacked_state(states, S, Q, norm, fail, leak, split_P):
-    """The B one-env snapshots parsed and concatenated section by section along the env axis."""
-    parts = [statelayout.parse(s, 1, S, Q, norm, fail, leak, split_P=split_P) for s in states]
-    out = {name: np.concatenate([p[name] for p in parts]) for name in parts[0]}
-    out["_live_ring"] = np.concatenate([statelayout.live_ring(p, 1, S, Q) for p in parts])
-    if split_P:
-        out["_live_pend"] = np.concatenate([statelayout.live_pend(p, 1, S, split_P) for p in parts])
-    return out
+def check_kernel(lib, env, mapping, kw, expect):
+    """parity.check_dispatch with the case's expected kernel form as the default."""
+    def default(kern, names):
+        if expect == "env_lane":
+            assert kern == ENV_LANE and names.get(0, "").startswith("dynamics_kernel<"), (kern, names)
+        elif expect == "group":
+            assert kern == GROUP and names.get(0, "").startswith("dynamics_group_"), (kern, names)
+        elif expect == "fused":
+            assert kern == GROUP and names.get(4, "").startswith("fused_step_kernel<"), (kern, names)
+        elif expect == "step_wave":
+            assert kern == WAVE and names.get(4, "").startswith("step_wave_kernel<"), (kern, names)
+        elif expect == "wave_split":  # next-step auto-reset handles step in two launches
+            assert kern == WAVE and names.get(0, "").startswith("dynamics_wave_kernel<"), (kern, names)
+        else:
+            raise AssertionError(expect)
 
-
-def compare_state(h_gpu, ora, B, S, cfg):
-    """Every state word of the handle against the stacked oracle state (ring / pend: the live
-    entries only, stale slots beyond the counts are not state).  Returns the oracle side."""
-    Q, norm, fail = cfg.queue_capacity, bool(cfg.normalize_obs), cfg.fail_prob > 0
-    leak, sp = statelayout.has_leak(cfg), statelayout.split_p(cfg)
-    g = statelayout.parse(h_gpu.state_bytes(), B, S, Q, norm, fail, leak, split_P=sp)
-    o = stacked_state(ora.states(), S, Q, norm, fail, leak, sp)
-    for name in g:
-        if name in ("ring", "pend"):
-            continue
-        np.testing.assert_array_equal(g[name], o[name], err_msg=name)
-    np.testing.assert_array_equal(statelayout.live_ring(g, B, S, Q), o["_live_ring"])
-    if sp:
-        np.testing.assert_array_equal(statelayout.live_pend(g, B, S, sp), o["_live_pend"])
-    return o
-
-
-def actions(rng, B, S, kw):
-    if kw.get("action_type") == "continuous":
-        return rng.uniform(-1.0, 11.0, (B, S)).astype(np.float32)
-    return rng.integers(-3, 3, (B, S)).astype(np.int64)
-
-
-def step_both(env, ora, a, k):
-    og, rg, dg, info = env.step(torch.from_numpy(a), assign_counts=True)
-    oo, ro, do, ao = ora.step(a)
-    np.testing.assert_array_equal(info["assign_counts"].cpu().numpy(), ao, err_msg=f"assign step {k}")
-    np.testing.assert_array_equal(og.cpu().numpy(), oo, err_msg=f"obs step {k}")
-    np.testing.assert_array_equal(rg.cpu().numpy(), ro, err_msg=f"reward step {k}")
-    np.testing.assert_array_equal(dg.cpu().numpy().astype(np.uint8), do, err_msg=f"done step {k}")
-
-
-def check_kernel(lib, env, S, mapping, kw, expect):
-    """The kernel form that ran, by lbsim_dynamics_kernel and the launch names of the last step;
-    under the child runs' LBSIM_DYN_GROUP_LANES / LBSIM_DYN_WAVE overrides, the forced form."""
-    kern = lib.load().lbsim_dynamics_kernel(env.handle.h)
-    names = lib.launch_names(env.handle)
-    lanes, wave = os.environ.get("LBSIM_DYN_GROUP_LANES"), os.environ.get("LBSIM_DYN_WAVE")
-    fits_wave = (mapping != "env" and S <= 8 and kw.get("queue_capacity", 32) <= 32
+    fits_wave = (mapping != "env" and env.cfg.num_servers <= 8 and kw.get("queue_capacity", 32) <= 32
                  and kw.get("assign_policy") != "alias" and not kw.get("fail_prob")
                  and not kw.get("lost_fin_prob"))
-    if lanes and mapping != "env":
-        assert kern == GROUP, (kern, names)
-        if kw.get("step_kernel") != "fused":
-            assert names.get(0, "").startswith(f"dynamics_group_kernel<{lanes},"), names
-        return
-    if wave == "1" and fits_wave:
-        assert kern == WAVE, (kern, names)
-        assert (names.get(0, "").startswith("dynamics_wave_kernel<")
-                or names.get(4, "").startswith("step_wave_kernel<")), names
-        return
-    if expect == "env_lane":
-        assert kern == ENV_LANE and names.get(0, "").startswith("dynamics_kernel<"), (kern, names)
-    elif expect == "group":
-        assert kern == GROUP and names.get(0, "").startswith("dynamics_group_"), (kern, names)
-    elif expect == "fused":
-        assert kern == GROUP and names.get(4, "").startswith("fused_step_kernel<"), (kern, names)
-    elif expect == "step_wave":
-        assert kern == WAVE and names.get(4, "").startswith("step_wave_kernel<"), (kern, names)
-    elif expect == "wave_split":  # next-step auto-reset handles step in two launches
-        assert kern == WAVE and names.get(0, "").startswith("dynamics_wave_kernel<"), (kern, names)
-    else:
-        raise AssertionError(expect)
+    group = None if mapping == "env" else "" if kw.get("step_kernel") == "fused" else "dynamics_group_kernel"
+    parity.check_dispatch(lib, env, default, forced_group=group, forced_wave=fits_wave)
 
 
-def run_vs_oracles(lib, oracle_mod, B, S, kw, mapping, expect, seed, r, mu, env_kw=None,
-                   steps=12, post_steps=4):
-    """12 steps, a masked reset of every third env, 4 more steps: outputs every step, the state
-    after step 12 and at the end.  Returns the stacked oracle state after step 12."""
+def run_vs_oracles(lib, oracle_mod, B, S, kw, mapping, expect, seed, r, mu, env_kw=None):
+    """parity.run_vs_reference on a handle with the rates r / mu against per-env oracles, the
+    kernel form checked after step 12.  Returns the stacked oracle state after step 12."""
     from marllb_amd.env import VecLoadBalanceEnv
     kw = dict(kw)
-    gkw = dict(kw)
     if mapping == "server-fused":
-        mapping, gkw["step_kernel"], kw["step_kernel"] = "server", "fused", "fused"
+        mapping, kw["step_kernel"] = "server", "fused"
     env = VecLoadBalanceEnv(B, S, device="cuda:0", dyn_mapping=mapping,
-                            **{"autoreset": False, **(env_kw or {})}, **gkw)
+                            **{"autoreset": False, **(env_kw or {})}, **kw)
     okw = dict(kw)
     if env.next_step:
         okw["next_step_reset"] = True
     ora = PerEnvOracles(oracle_mod, B, S, okw, r, mu)
     env.set_rates(None if r is None else r, None if mu is None else torch.from_numpy(mu))
-    np.testing.assert_array_equal(env.reset().cpu().numpy(), ora.reset())
-    rng = np.random.default_rng(seed)
-    for k in range(steps):
-        step_both(env, ora, actions(rng, B, S, kw), k)
-    check_kernel(lib, env, S, mapping, kw, expect)
-    mid = compare_state(env.handle, ora, B, S, env.cfg)
-    mask = (np.arange(B) % 3 == 0).astype(np.uint8)
-    og = env.reset(mask=torch.from_numpy(mask)).cpu().numpy()
-    np.testing.assert_array_equal(og, ora.reset(mask=mask, obs=og))
-    for k in range(post_steps):
-        step_both(env, ora, actions(rng, B, S, kw), steps + k)
-    compare_state(env.handle, ora, B, S, env.cfg)
+    mid = parity.run_vs_reference(env, ora, kw, seed,
+                                  hook=lambda e: check_kernel(lib, e, mapping, kw, expect))
     ora.close()
     env.close()
     return mid
@@ -242,15 +166,9 @@ def test_bit_exact_vs_per_env_oracles(lib, oracle_mod, case):
 
 def _child(env_over):
     """This file's S <= 4 cases in a child process (the overrides are read once per process)."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ks = [f"test_bit_exact_vs_per_env_oracles[{c}]" for c, v in CASES.items() if v[1] <= 4]
     assert len(ks) >= 8
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p",
-                        "no:cacheprovider"] +
-                       [os.path.join(root, "tests", "test_env_rates.py") + "::" + k for k in ks],
-                       cwd=root, env={**os.environ, **env_over}, capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    parity.run_cases_in_child("test_env_rates.py", ks, env_over)
 
 
 @gpu
@@ -302,7 +220,7 @@ def test_mid_run_change(lib, oracle_mod):
     ora.close()
     for k in range(6, 12):
         step_both(env, new, actions(rng, B, S, kw), k)
-    compare_state(env.handle, new, B, S, env.cfg)
+    compare_state(env.handle, new, env.cfg)
     a, m = env.rates
     np.testing.assert_array_equal(a.cpu().numpy(), r1)
     np.testing.assert_array_equal(m.cpu().numpy(), mu1)
@@ -498,8 +416,7 @@ def test_lost_fin_overflow_accessor(lib):
         env.step(a)
     over = env.handle.lost_fin_overflow()
     assert over.shape == (B,) and over.dtype == np.uint32 and (over > 0).any()
-    sp = statelayout.split_p(env.cfg)
-    st = statelayout.parse(env.get_state(), B, S, env.cfg.queue_capacity, False, split_P=sp)
+    st = statelayout.parse_cfg(env.get_state(), env.cfg)
     np.testing.assert_array_equal(over, st["lf_over"])
     env.close()
     plain = VecLoadBalanceEnv(B, S, device="cuda:0", seed=2)

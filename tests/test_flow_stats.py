@@ -8,22 +8,19 @@ under next-step auto-reset an env whose previous step returned done contributes 
 step that resets it; under same-step auto-reset the oracle's state is read before its masked
 reset is applied.  Every comparison with the device is exact.
 """
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from marllb_amd import flowstats
-from tests import statelayout
+from tests import parity, statelayout
+from tests.parity import GROUP, actions, lib, step_both  # noqa: F401  (lib: the fixture)
+from tests.test_step_plan import run_probe
 
 torch = pytest.importorskip("torch")
 gpu = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 K = 128
 Q_PPM = [500000, 900000, 990000, 1000000]
-GROUP, TWO_LAUNCH = 1, 2  # LBSIM_DYN_KERNEL_GROUP, kStepTwoLaunch
+TWO_LAUNCH = 2  # kStepTwoLaunch
 
 
 # ------------------------------------------------------------------ the two rules (no GPU)
@@ -115,19 +112,9 @@ def test_abi_version_stays_and_null_handles_are_rejected():
 
 # ------------------------------------------------------------------ the plan (no GPU)
 
-def _probe(tmp, name, rows):
-    import json
-    from marllb_amd import build
-    exe = str(tmp / name)
-    subprocess.run([build.hipcc(), "-x", "c++", "-std=c++17", "-Wall", "-o", exe,
-                    os.path.join(HERE, name + ".cpp")], check=True)
-    text = "".join(" ".join(map(str, r)) + "\n" for r in rows)
-    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout
-    return [json.loads(line) for line in out.splitlines()]
-
-
 def _plan_row(B, S, simds=1024, **over):
-    """plan_probe's 20 input integers (tests/golden/step_plan.jsonl's header order)."""
+    """plan_probe's first 20 input integers (tests/golden/step_plan.jsonl's header order); the
+    21st, flow_stats, is appended by the test (absent: 0)."""
     f = dict(B=B, S=S, Q=32, policy=0, trace=0, fail=0, leak=0, split=0, res_vpp=0, dur_plane=0,
              next_reset=0, dyn_mapping=0, step_kernel=0, simds=simds, group_lanes_set=0,
              group_lanes=0, dyn_wave=-1, dyn_epw=0, ov_step_kernel=0, step_wave_occ=0)
@@ -146,9 +133,9 @@ def test_statistics_handles_plan_the_full_group_kernel(tmp_path):
             _plan_row(65536, 4, next_reset=1),
             _plan_row(8192, 16, simds=416),
             _plan_row(19, 2, Q=32)]
-    plain = _probe(tmp_path, "plan_probe", rows)
-    off = _probe(tmp_path, "flow_stats_plan_probe", [r + [0] for r in rows])
-    on = _probe(tmp_path, "flow_stats_plan_probe", [r + [1] for r in rows])
+    plain = run_probe(tmp_path, rows)
+    off = run_probe(tmp_path, [r + [0] for r in rows])
+    on = run_probe(tmp_path, [r + [1] for r in rows])
     assert off == plain  # the flag clear: the dispatch of today, field for field
     assert {p["form"] for p in plain} == {0, 1, 2} and {p["dyn"]["kernel"] for p in plain} == {0, 1, 2}
     for r, p, q in zip(rows, on, plain):
@@ -161,8 +148,7 @@ def test_statistics_handles_plan_the_full_group_kernel(tmp_path):
         assert p["obs"] == q["obs"] and p["reset_obs"] == q["reset_obs"]  # the observe is unaffected
     # a handle that is full already plans the same with and without the flag
     full = [_plan_row(67, 4, res_vpp=1), _plan_row(65536, 4, res_vpp=1, step_kernel=2)]
-    assert (_probe(tmp_path, "flow_stats_plan_probe", [r + [1] for r in full])
-            == _probe(tmp_path, "plan_probe", full))
+    assert run_probe(tmp_path, [r + [1] for r in full]) == run_probe(tmp_path, full)
 
 
 # ------------------------------------------------------------------ the oracle-side reference
@@ -202,8 +188,7 @@ class OracleFlows:
         cfg, B, S = self.cfg, self.B, self.S
         fail = cfg.fail_prob > 0
         sp = statelayout.split_p(cfg)
-        d = statelayout.parse(self.ora.state_bytes(), B, S, cfg.queue_capacity,
-                              bool(cfg.normalize_obs), fail, statelayout.has_leak(cfg), split_P=sp)
+        d = statelayout.parse_cfg(self.ora.state_bytes(), cfg)
         count = d["res_count_dur"] if sp else d["res_count"]
         rec = d["res_dur"] if sp else d["res_fct"]  # lost-FIN: the real tc - ta
         down = d["down"].reshape(B, S) != 0 if fail else None
@@ -290,29 +275,13 @@ def check_against_values(ref, qs, qe):
                     assert qs[b, s, i] == 0
 
 
-def actions(rng, B, S, kw):
-    if kw.get("action_type") == "continuous":
-        return rng.uniform(-1.0, 11.0, (B, S)).astype(np.float32)
-    return rng.integers(-3, 3, (B, S)).astype(np.int64)
+def check_full_kernel(lib, env):
+    """The full group kernel ran; in the child run, at the forced group width."""
+    def default(kern, names):
+        assert names.get(0, "").startswith("dynamics_group_full_kernel<"), names
+        assert kern == GROUP
 
-
-def step_both(env, ref, a, k):
-    og, rg, dg, info = env.step(torch.from_numpy(a), assign_counts=True)
-    oo, ro, do, ao = ref.step(a)
-    np.testing.assert_array_equal(info["assign_counts"].cpu().numpy(), ao, err_msg=f"assign step {k}")
-    np.testing.assert_array_equal(og.cpu().numpy(), oo, err_msg=f"obs step {k}")
-    np.testing.assert_array_equal(rg.cpu().numpy(), ro, err_msg=f"reward step {k}")
-    np.testing.assert_array_equal(dg.cpu().numpy().astype(np.uint8), do, err_msg=f"done step {k}")
-    return do
-
-
-def check_full_kernel(lib, env, S):
-    names = lib.launch_names(env.handle)
-    assert names.get(0, "").startswith("dynamics_group_full_kernel<"), names
-    assert lib.load().lbsim_dynamics_kernel(env.handle.h) == GROUP
-    lanes = os.environ.get("LBSIM_DYN_GROUP_LANES")
-    if lanes and int(lanes) >= S:  # the child run: the forced group width
-        assert names[0].startswith(f"dynamics_group_full_kernel<{lanes},"), names
+    parity.check_dispatch(lib, env, default, forced_group="dynamics_group_full_kernel")
 
 
 ALIAS = {"assign_policy": "alias", "action_type": "continuous"}
@@ -353,14 +322,6 @@ def make_pair(oracle_mod, B, S, kw, env_kw, offset=0, **extra):
     return env, ref
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test run without a HIP device")
-    from marllb_amd import _lib
-    return _lib
-
-
 @gpu
 @pytest.mark.parametrize("case", list(CASES))
 def test_statistics_equal_the_oracles_records(lib, oracle_mod, case):
@@ -375,13 +336,13 @@ def test_statistics_equal_the_oracles_records(lib, oracle_mod, case):
     for k in range(steps):
         dones += int(step_both(env, ref, actions(rng, B, S, kw), k).sum())
         qs, qe = compare_stats(env, ref, f"step {k}")
-    check_full_kernel(lib, env, S)
+    check_full_kernel(lib, env)
     check_against_values(ref, qs, qe)
     assert ref.count.sum() > 20 * B  # the case is not vacuous
     if env_kw:
         assert dones >= 2 * B  # episodes ended and restarted inside the run
     if "queue_capacity" in kw and kw["queue_capacity"] == 4:
-        st = statelayout.parse(ref.ora.state_bytes(), B, S, 4, False)
+        st = statelayout.parse_cfg(ref.ora.state_bytes(), ref.cfg)
         assert (st["dropped"] > 0).any()  # flows were dropped, and none of them counted
     if case == "19x2-long-flows":
         assert ref.max_us.max() > 30_000_000 and (ref.hist[:, :, 176:].sum() > 0)  # the top octaves
@@ -396,15 +357,9 @@ def test_statistics_equal_the_oracles_records(lib, oracle_mod, case):
 
 def _child(env_over):
     """This file's S <= 4 cases in a child process (the overrides are read once per process)."""
-    root = os.path.dirname(HERE)
     ks = [f"test_statistics_equal_the_oracles_records[{c}]" for c, v in CASES.items() if v[1] <= 4]
     assert len(ks) >= 10
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p",
-                        "no:cacheprovider"] +
-                       [os.path.join(root, "tests", "test_flow_stats.py") + "::" + k for k in ks],
-                       cwd=root, env={**os.environ, **env_over}, capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    parity.run_cases_in_child("test_flow_stats.py", ks, env_over)
 
 
 @gpu

@@ -221,15 +221,8 @@ def test_other_tile_forms_match_modules(env):
     """The one-wave-per-agent and layer-split QMIX kernels, the 16 / 32 / 64-env tiles (SAC's
     default is 32 since round 6, the QMIX tile kernel's 16; selected once per process by the
     environment, so checked in a child process) pass the same parity tests as the defaults."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p",
-                        "no:cacheprovider", os.path.join(root, "tests", "test_fused_policy.py"),
-                        "-k", "matches_module"],
-                       cwd=root, env={**os.environ, **env}, capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    from tests.parity import run_cases_in_child
+    run_cases_in_child("test_fused_policy.py", "matches_module", env, timeout=300)
 
 
 @pytest.mark.gpu

@@ -11,25 +11,13 @@ import os
 import numpy as np
 import pytest
 
-from tests import statelayout
+from tests import parity, statelayout
+from tests.parity import dev, lib  # noqa: F401  (lib: the fixture)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 FIELD_COL = {"flow_duration_avg_decay": 10, "n_flow_on": 0, "fct_mean": 1, "no_such_field": -1}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU test run without a HIP device")
-    from marllb_amd import _lib
-    return _lib
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return t.to("cuda:0") if dtype is None else t.to("cuda:0", dtype)
 
 
 # ------------------------------------------------------------------ stateless kernels
@@ -308,65 +296,14 @@ def resolve_kw(kw):
     return kw
 
 
-def _actions(rng, B, S, cfgkw):
-    if cfgkw.get("action_type") == "continuous":
-        a = rng.uniform(-1.0, 11.0, (B, S)).astype(np.float32)
-        a[rng.random((B, S)) < cfgkw.get("_nan_actions", 0.0)] = np.nan
-        return a
-    n = len(cfgkw.get("discrete_weights", [1, 1.5, 2]))
-    return rng.integers(-n, n, (B, S)).astype(np.int64)
-
-
-def _compare_state(h_gpu, ora, B, S, Q, norm, fail=False, leak=False, split_P=0):
-    g = statelayout.parse(h_gpu.state_bytes(), B, S, Q, norm, fail, leak, split_P=split_P)
-    o = statelayout.parse(ora.state_bytes(), B, S, Q, norm, fail, leak, split_P=split_P)
-    for name in g:
-        if name in ("ring", "pend"):
-            continue
-        np.testing.assert_array_equal(g[name], o[name], err_msg=name)
-    np.testing.assert_array_equal(statelayout.live_ring(g, B, S, Q), statelayout.live_ring(o, B, S, Q))
-    if split_P:  # the pending lost-FIN guesses in their rings
-        np.testing.assert_array_equal(statelayout.live_pend(g, B, S, split_P),
-                                      statelayout.live_pend(o, B, S, split_P))
-
-
 def _run_vs_oracle(oracle_mod, B, S, kw, akw, case, mapping="auto", steps=12, post_steps=4,
                    threads=4, autoreset=False):
-    """Step a VecLoadBalanceEnv and the oracle side by side from the same seeds: observations,
-    rewards, done and per-server assignment counts every step, the full device state word for word
-    after `steps` steps and again after a masked reset of every third env and `post_steps` more
-    steps.  Returns the env (open) for further checks."""
+    """parity.run_vs_reference on a VecLoadBalanceEnv and one oracle of the same config.  Returns
+    the env (open) for further checks."""
     from marllb_amd.env import VecLoadBalanceEnv, make_config
     env = VecLoadBalanceEnv(B, S, device="cuda:0", autoreset=autoreset, dyn_mapping=mapping, **kw)
     ora = oracle_mod.OracleEnv(make_config(B, S, **kw), threads=threads, trace=kw.get("trace"))
-    Q, norm, fail = env.cfg.queue_capacity, bool(env.cfg.normalize_obs), env.cfg.fail_prob > 0
-    leak = statelayout.has_leak(env.cfg)
-    sp = statelayout.split_p(env.cfg)
-    obs_g = env.reset().cpu().numpy()
-    obs_o = ora.reset()
-    np.testing.assert_array_equal(obs_g, obs_o)
-    rng = np.random.default_rng(case)
-    for k in range(steps):
-        a = _actions(rng, B, S, akw)
-        og, rg, dg, info = env.step(torch.from_numpy(a), assign_counts=True)
-        oo, ro, do, ao = ora.step(a)
-        np.testing.assert_array_equal(info["assign_counts"].cpu().numpy(), ao, err_msg=f"assign step {k}")
-        np.testing.assert_array_equal(og.cpu().numpy(), oo, err_msg=f"obs step {k}")
-        np.testing.assert_array_equal(rg.cpu().numpy(), ro, err_msg=f"reward step {k}")
-        np.testing.assert_array_equal(dg.cpu().numpy().astype(np.uint8), do)
-    _compare_state(env.handle, ora, B, S, Q, norm, fail, leak, sp)
-    # masked reset of every third env, then more steps
-    mask = (np.arange(B) % 3 == 0).astype(np.uint8)
-    og = env.reset(mask=torch.from_numpy(mask)).cpu().numpy()
-    oo = ora.reset(mask=mask, obs=og.copy())
-    np.testing.assert_array_equal(og, oo)
-    for k in range(post_steps):
-        a = _actions(rng, B, S, akw)
-        og, rg, dg, _ = env.step(torch.from_numpy(a))
-        oo, ro, do, _ = ora.step(a)
-        np.testing.assert_array_equal(og.cpu().numpy(), oo)
-        np.testing.assert_array_equal(rg.cpu().numpy(), ro)
-    _compare_state(env.handle, ora, B, S, Q, norm, fail, leak, sp)
+    parity.run_vs_reference(env, ora, akw, case, steps, post_steps, levels=True)
     ora.close()
     return env
 
@@ -390,14 +327,9 @@ def test_simulator_bit_exact_vs_oracle(lib, oracle_mod, case, mapping):
     env.close()
 
 
-def _simds():
-    return 4 * torch.cuda.get_device_properties(0).multi_processor_count
-
-
 def _expected_step_kernels(B, S, simds):
-    """The default dispatch (lbsim_api.hip use_step_wave, lbsim_internal.h dyn_wave_ok /
-    dyn_group_lanes, lbsim_step.hip launch_w) of a SED, Poisson, Q = 32 handle: {profile class:
-    kernel-name prefix} of one step."""
+    """The default dispatch (make_plan in csrc/lbsim_plan.h, stated here independently of it) of
+    a SED, Poisson, Q = 32 handle: {profile class: kernel-name prefix} of one step."""
     if B <= 4 * simds and S <= 8:  # one launch; S = 5-8: both chunks observed by the wave
         ng = 1 if S <= 2 else 2 if S <= 4 else 4
         occ = 2 if B <= 2 * simds else 4
@@ -420,7 +352,7 @@ def test_configs1_default_dispatch_4096x4(lib, oracle_mod):
     kw = {"seed": 4096}
     env = _run_vs_oracle(oracle_mod, B, S, kw, {}, 77, threads=8)
     names = _lib.launch_names(env.handle)
-    for cls, pfx in _expected_step_kernels(B, S, _simds()).items():
+    for cls, pfx in _expected_step_kernels(B, S, parity.simds()).items():
         assert names.get(cls, "").startswith(pfx), (names, pfx)
     env.close()
 
@@ -433,13 +365,13 @@ def test_dispatch_boundaries_bit_exact(lib, oracle_mod, S, where):
     groups; S = 8: the two-chunk forms).  The kernel that ran is checked by
     name (lbsim_launch_names), the results against the oracle on every env."""
     from marllb_amd import _lib
-    simds = _simds()
+    n = parity.simds()
     k, plus = (2, 0) if where == "2s" else (2, 1) if where == "2s+1" else (4, 0) if where == "4s" else (4, 1)
-    B = k * simds + plus
+    B = k * n + plus
     kw = {"seed": 500 + B + S, "assign_policy": "sed"}
     env = _run_vs_oracle(oracle_mod, B, S, kw, {}, B + S, steps=6, post_steps=2, threads=8)
     names = _lib.launch_names(env.handle)
-    for cls, pfx in _expected_step_kernels(B, S, simds).items():
+    for cls, pfx in _expected_step_kernels(B, S, n).items():
         assert names.get(cls, "").startswith(pfx), (B, S, names, pfx)
     env.close()
 
@@ -452,21 +384,13 @@ def test_step_wave_occupancy_forms_bit_exact(occ):
     rings, normalisation off) runs on the OCC-4 form that serves 2-4 envs per SIMD -- BASELINE
     configs[1]'s 4096 x 4 -- and on the OCC-2 form, the two-chunk S = 5-8 forms included.  Child
     process (read once per process)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ks = [f"test_simulator_bit_exact_vs_oracle[{c}-{m}]" for c in range(len(CONFIGS))
           for m in ("server", "server-fused")
           if CONFIGS[c]["S"] <= 8 and CONFIGS[c]["B"] <= 4096
           and CONFIGS[c]["kw"].get("queue_capacity", 32) <= 32
           and CONFIGS[c]["kw"].get("assign_policy") != "alias"]
     assert len(ks) >= 20
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p",
-                        "no:cacheprovider"] +
-                       [os.path.join(root, "tests", "test_gpu_parity.py") + "::" + k for k in ks],
-                       cwd=root, env={**os.environ, "LBSIM_STEP_WAVE_OCC": occ},
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    parity.run_cases_in_child("test_gpu_parity.py", ks, {"LBSIM_STEP_WAVE_OCC": occ})
 
 
 @pytest.mark.parametrize("lanes,epw", [("4", ""), ("8", ""), ("16", ""), ("4", "13"), ("8", "3")])
@@ -478,18 +402,11 @@ def test_wider_groups_bit_exact(lanes, epw):
     groups.  epw (LBSIM_DYN_EPW): fewer envs per wave than 64 / lanes (lanes of the groups past it
     idle), e.g. 13 4-lane envs per wave.  The settings are read once per process, so the cases run
     in a child process."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ks = [f"test_simulator_bit_exact_vs_oracle[{c}-{m}]" for c in range(len(CONFIGS))
           for m in ("server", "server-fused") if CONFIGS[c]["S"] <= int(lanes)]
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p",
-                        "no:cacheprovider"] +
-                       [os.path.join(root, "tests", "test_gpu_parity.py") + "::" + k for k in ks],
-                       cwd=root, env={**os.environ, "LBSIM_DYN_GROUP_LANES": lanes,
-                                      **({"LBSIM_DYN_EPW": epw} if epw else {})},
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    parity.run_cases_in_child("test_gpu_parity.py", ks,
+                              {"LBSIM_DYN_GROUP_LANES": lanes,
+                               **({"LBSIM_DYN_EPW": epw} if epw else {})})
 
 
 @pytest.mark.parametrize("step", ["auto", "fused"])
@@ -500,21 +417,14 @@ def test_wave_kernel_bit_exact(step):
     launch then an observe launch; fused (LBSIM_STEP_KERNEL=fused, opt-in): one step_wave_kernel
     launch (dynamics then observe per wave).  Resets use dynamics_wave_kernel in both.  The
     settings are read once per process, so the cases run in a child process."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ks = [f"test_simulator_bit_exact_vs_oracle[{c}-{m}]" for c in range(len(CONFIGS))
           for m in ("server", "server-fused")
           if CONFIGS[c]["S"] <= 8 and CONFIGS[c]["kw"].get("queue_capacity", 32) <= 32
           and CONFIGS[c]["kw"].get("assign_policy") != "alias"]
     assert len(ks) >= 20
-    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p",
-                        "no:cacheprovider"] +
-                       [os.path.join(root, "tests", "test_gpu_parity.py") + "::" + k for k in ks],
-                       cwd=root, env={**os.environ, "LBSIM_DYN_WAVE": "1",
-                                      **({"LBSIM_STEP_KERNEL": "fused"} if step == "fused" else {})},
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    parity.run_cases_in_child("test_gpu_parity.py", ks,
+                              {"LBSIM_DYN_WAVE": "1",
+                               **({"LBSIM_STEP_KERNEL": "fused"} if step == "fused" else {})})
 
 
 @pytest.mark.parametrize("S,world,B", [(4, 2, 200), (8, 4, 1003), (8, 8, 8400), (16, 8, 777)])
@@ -586,7 +496,7 @@ def test_full_size_properties(lib, oracle_mod):
         assert torch.isfinite(obs).all()
         assert (rew >= 1.0 / S - 1e-6).all() and (rew <= 1.0).all()  # Jain range
         assert not done.any()
-    st = statelayout.parse(env.handle.state_bytes(), B, S, env.cfg.queue_capacity, False)
+    st = statelayout.parse_cfg(env.handle.state_bytes(), env.cfg)
     # conservation: every arrival drawn (arr_idx counts arrivals since reset) is assigned or dropped
     expected_rate = 500.0 * 0.25
     per_step = tot.sum().item() / (B * steps)
@@ -673,7 +583,7 @@ def test_full_size_trace_replay_c3(lib, oracle_mod):
         obs, rew, done, info = env.step(torch.from_numpy(a), assign_counts=True)
         tot += info["assign_counts"].sum(1)
         assert torch.isfinite(obs).all() and not done.any()
-    st = statelayout.parse(env.handle.state_bytes(), B, S, env.cfg.queue_capacity, False)
+    st = statelayout.parse_cfg(env.handle.state_bytes(), env.cfg)
     # arrivals since reset = rows consumed from each env's offset (warm-up included)
     arrived = tot + torch.from_numpy(st["dropped"].astype(np.int64)).cuda()
     idx = torch.from_numpy(st["arr_idx"].astype(np.int64)).cuda()
@@ -692,9 +602,9 @@ def test_dynamics_kernel_dispatch(lib):
     """lbsim_dynamics_kernel names the kernel the launches use: one wave per env for small S <= 8
     batches (at most 4 envs per SIMD for S <= 4, 2 for S <= 8, queue capacity <= 32, not ALIAS),
     server-per-lane groups otherwise, one lane per env when asked for.  The batch limits are in
-    envs per SIMD of this device (dyn_wave_ok's rule), not a 256-CU constant."""
+    envs per SIMD of this device (make_plan's rule), not a 256-CU constant."""
     from marllb_amd.env import VecLoadBalanceEnv
-    simds = _simds()
+    simds = parity.simds()
     cases = [(dict(num_envs=257, num_servers=4), 2), (dict(num_envs=1, num_servers=4), 2),
              (dict(num_envs=4 * simds + 1, num_servers=4), 1),
              (dict(num_envs=64, num_servers=8), 2),

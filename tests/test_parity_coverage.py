@@ -17,7 +17,8 @@ import pytest
 from tests import statelayout
 
 pytest.importorskip("torch")
-from tests.test_gpu_parity import CONFIGS, _actions, resolve_kw  # noqa: E402
+from tests.parity import actions  # noqa: E402
+from tests.test_gpu_parity import CONFIGS, resolve_kw  # noqa: E402
 
 PACK_LIMIT = (1 << 25) - 1
 
@@ -40,10 +41,8 @@ def run_case(oracle_mod, case, steps=12):
     paths = np.zeros(4, np.int64)  # recomputed chunks: register path full / register path partly
     #                                  filled / general path with a big sample / general with n < 8
     for _ in range(steps):
-        ora.step(_actions(rng, B, S, c["kw"]))  # the GPU test's action stream
-        st = statelayout.parse(ora.state_bytes(), B, S, cfg.queue_capacity, bool(cfg.normalize_obs),
-                               cfg.fail_prob > 0, statelayout.has_leak(cfg),
-                               split_P=statelayout.split_p(cfg))
+        ora.step(actions(rng, B, S, c["kw"], levels=True))  # the GPU test's action stream
+        st = statelayout.parse_cfg(ora.state_bytes(), cfg)
         max_q = max(max_q, int((st["hc"] >> 16).max()))
         per_server = np.unpackbits(st["chg"].view(np.uint8)).reshape(B, S, 128).sum(2)
         written.append(per_server.sum(1))  # slots written per env (all its servers)

@@ -34,14 +34,21 @@ def table(golden_dir):
     return head, rows
 
 
-@pytest.fixture(scope="module")
-def probe_rows(table, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("plan") / "plan_probe")
-    subprocess.run([build.hipcc(), "-x", "c++", "-std=c++17", "-Wall", "-o", exe,
-                    os.path.join(HERE, "plan_probe.cpp")], check=True)
-    text = "".join(" ".join(map(str, inp)) + "\n" for inp, _ in table[1])
+def run_probe(tmp, rows):
+    """make_plan's answers to rows of 20 or 21 integers (the 21st: flow_stats), from plan_probe
+    compiled into the directory tmp (once per directory)."""
+    exe = str(tmp / "plan_probe")
+    if not os.path.exists(exe):
+        subprocess.run([build.hipcc(), "-x", "c++", "-std=c++17", "-Wall", "-o", exe,
+                        os.path.join(HERE, "plan_probe.cpp")], check=True)
+    text = "".join(" ".join(map(str, r)) + "\n" for r in rows)
     out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout
     return [json.loads(line) for line in out.splitlines()]
+
+
+@pytest.fixture(scope="module")
+def probe_rows(table, tmp_path_factory):
+    return run_probe(tmp_path_factory.mktemp("plan"), [inp for inp, _ in table[1]])
 
 
 def _flat(plan):

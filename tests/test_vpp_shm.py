@@ -185,7 +185,7 @@ def test_gpu_simulator_as_live_vpp(oracle_mod, tmp_path):
                                                       else d, f"lbsim_t{os.getpid()}_{{}}"), n=n)
     try:
         tv, nf, ts = pub.export()
-        st = statelayout.parse(ora.state_bytes(), B, S, env.cfg.queue_capacity, False)
+        st = statelayout.parse_cfg(ora.state_bytes(), env.cfg)
         cnt = np.minimum(st["res_count"].reshape(B, S), 128)
         words = {0: st["res_fct"].reshape(B, S, 128), 1: st["res_dur"].reshape(B, S, 128)}
         tsw = st["res_ts"].reshape(B, S, 128)
@@ -271,8 +271,7 @@ def test_gpu_vpp_export_reservoir_modes(oracle_mod, kw):
         a = rng.integers(0, 3, (B, S)).astype(np.int64)
         env.step(torch.from_numpy(a))
         ora.step(a)
-        st = statelayout.parse(ora.state_bytes(), B, S, cfg.queue_capacity, False,
-                               split_P=statelayout.split_p(cfg))
+        st = statelayout.parse_cfg(ora.state_bytes(), cfg)
         want, ts_w = _tv_from_oracle_state(st, B, S, vpp)
         pub = vs.VppPublisher(env, path_fmt=os.path.join("/dev/shm", f"lbsim_m{os.getpid()}_{{}}"),
                               n=B)
@@ -302,11 +301,11 @@ def test_gpu_upstream_feature_mode(oracle_mod):
     B, S = 40, 4
     kw = dict(seed=5150, reward_metric="variance")
     env = VecLoadBalanceEnv(B, S, device="cuda:0", autoreset=False, feature_mode="upstream", **kw)
-    ora = oracle_mod.OracleEnv(make_config(B, S, **kw), threads=2)
-    Q = env.cfg.queue_capacity
+    cfg = make_config(B, S, **kw)
+    ora = oracle_mod.OracleEnv(cfg, threads=2)
 
     def expect(o_obs):
-        st = statelayout.parse(ora.state_bytes(), B, S, Q, False)
+        st = statelayout.parse_cfg(ora.state_bytes(), cfg)
         tv, ts = _tv_from_oracle_state(st, B, S)
         f = oracle_mod.vpp_features(tv.reshape(-1, 128, 2), ts, res_per_ts=2 * S)
         obs = o_obs.copy()
