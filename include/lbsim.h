@@ -453,6 +453,48 @@ int lbsim_clear_env_rates(lbsim_t* h);
 int lbsim_get_env_rates(lbsim_t* h, float* arrival_rate_out, float* server_rate_out,
                         void* stream);
 
+/* ---- rate schedules (non-stationary workloads) ----
+ * A handle may carry a rate schedule: `phases` (P) phases, each held for `steps_per_phase` (H)
+ * agent steps, cyclic (wrap != 0) or clamped at the last phase (wrap == 0).
+ * Phase rule: with k = the steps env b has completed in its current episode (its episode step at
+ * the launch of a step) and j = k / H, the step's dynamics use phase j % P (cyclic) or
+ * min(j, P - 1) (clamped) of env b's rows.  A reset always runs at phase 0: the first arrival
+ * draw, every warm-up step, and the in-launch reset of a next_step_reset handle.  A phase change
+ * acts exactly as a mid-run lbsim_set_env_rates: the arrival already drawn keeps its time and
+ * work, every later gap and service time uses the new phase's rates.
+ * lbsim_set_rate_schedule: arrival_rate [rows, P] and / or server_rate [rows, P, S], f32 DEVICE
+ * pointers, flows/s; rows = 1 (every env the same schedule) or B.  NULL: that quantity keeps, per
+ * env, the rate that was in force before the call (what lbsim_get_env_rates would have returned),
+ * constant over the phases.  Conversion, ranges and validation are lbsim_set_env_rates's: the call
+ * waits on `stream`; any value out of range returns LBSIM_EINVAL (the count in lbsim_last_error)
+ * and leaves the previous schedule or rates in force.  LBSIM_EINVAL: phases outside [1, 4096] or
+ * steps_per_phase < 1.  LBSIM_ESHAPE: rows neither 1 nor B.  LBSIM_ENOMEM: a table of more than
+ * 2^31 - 1 elements (B * P * S), or a failed allocation.  LBSIM_ENOTSUP: a non-NULL arrival_rate
+ * on a lost-FIN or TRACE handle (as lbsim_set_env_rates); server schedules are allowed on both.
+ * The handle stores the tables expanded to B rows, gap[B, P] and scale[B, P, S]: B * P * (S + 1)
+ * * 4 bytes, twice with the rates as given (what lbsim_get_env_rates returns), and all of it twice
+ * with the staging copies.  A scheduled handle's lbsim_step / lbsim_reset launch one small kernel
+ * in front of the dynamics that gathers each env's row at its phase.  The tables are allocated by
+ * the first call for a given P and never moved by later calls with the same P, which rewrite them
+ * in place: a step captured into a hipGraph after the first call sees the new values on replay.
+ * P, H and wrap are kernel arguments: changing any of them (a new P also moves the tables), or
+ * dropping the schedule, needs a new capture.  lbsim_step / lbsim_reset gain no allocation and no
+ * synchronisation.  The schedule is NOT part of the snapshot; the episode step is, so a scheduled
+ * handle that loads a state continues at that state's phase.
+ * On a scheduled handle lbsim_get_env_rates returns, per env, the rates its next step launch will
+ * use, and lbsim_set_env_rates / lbsim_clear_env_rates drop the schedule first (the per-env rates
+ * in force before the schedule are then the ones a NULL argument of lbsim_set_env_rates leaves as
+ * they are).
+ * lbsim_clear_rate_schedule: drops the schedule and goes back to the config's shared rates, as
+ * lbsim_clear_env_rates (the tables stay allocated and take the config's values).
+ * lbsim_rate_phase: phase_out[B] (int32 DEVICE) = the phase each env's next step launch will use
+ * (zeros on a handle without a schedule). */
+int lbsim_set_rate_schedule(lbsim_t* h, const float* arrival_rate, const float* server_rate,
+                            int32_t rows, int32_t phases, int32_t steps_per_phase, int32_t wrap,
+                            void* stream);
+int lbsim_clear_rate_schedule(lbsim_t* h);
+int lbsim_rate_phase(lbsim_t* h, int32_t* phase_out, void* stream);
+
 /*
  * Exact flow-completion-time statistics, opt-in per handle.  A handle with
  * them on counts every flow that completes during a STEP of an env, once, with its true

@@ -6,10 +6,11 @@ liblbsim.so), with the reference's Gym-style API on top.
 """
 from .env import FEATURE_NAMES, LoadBalanceEnv, LoadBalanceEnvGym, VecLoadBalanceEnv, make_config
 from .multi_agent import MultiAgentLoadBalanceEnv, VecMultiAgentLoadBalanceEnv
-from .randomize import sample_rates
+from .randomize import burst_schedule, diurnal_schedule, sample_rates, schedule_phase
 from .spaces import Box, MultiDiscrete
 
 __all__ = ["FEATURE_NAMES", "LoadBalanceEnv", "LoadBalanceEnvGym", "VecLoadBalanceEnv",
            "MultiAgentLoadBalanceEnv", "VecMultiAgentLoadBalanceEnv", "make_config", "Box",
-           "MultiDiscrete", "sample_rates"]
+           "MultiDiscrete", "sample_rates", "schedule_phase", "diurnal_schedule",
+           "burst_schedule"]
 __version__ = "0.1.0"

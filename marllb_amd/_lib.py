@@ -172,6 +172,10 @@ _SIGNATURES = {
     "lbsim_set_env_rates": (ctypes.c_int, [_P, _P, _P, _P]),
     "lbsim_clear_env_rates": (ctypes.c_int, [_P]),
     "lbsim_get_env_rates": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lbsim_set_rate_schedule": (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32, _P]),
+    "lbsim_clear_rate_schedule": (ctypes.c_int, [_P]),
+    "lbsim_rate_phase": (ctypes.c_int, [_P, _P, _P]),
     "lbsim_flow_stats_enable": (ctypes.c_int, [_P]),
     "lbsim_flow_stats_get": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "lbsim_flow_stats_quantiles": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),

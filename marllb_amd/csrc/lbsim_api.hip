@@ -74,6 +74,13 @@ struct lbsim {
   unsigned long long* stats_buf = nullptr;  // lbsim_step_stats sums (2 x u64)
   // lbsim_set_env_rates: one block, allocated by the first call and never moved (EnvRates below)
   float* rates_buf = nullptr;
+  bool rates_on = false;  // per-env rates are set (what dropping a schedule goes back to)
+  // lbsim_set_rate_schedule: the tables' block for sched_alloc_P phases (sched_floats below),
+  // moved only by a call with another P, and the schedule in force: sched_P phases (0: none), each
+  // held for sched_H steps, cyclic or clamped.
+  float* sched_buf = nullptr;
+  int sched_alloc_P = 0;
+  int sched_P = 0, sched_H = 0, sched_wrap = 0;
   // lbsim_flow_stats_enable: one block (sum_us, hist, count, max_us), allocated once, never moved
   void* flow_buf = nullptr;
   FlowStats flow{};  // its arrays (null pointers: statistics off)
@@ -376,6 +383,72 @@ __global__ void __launch_bounds__(256)
   if ((threadIdx.x & 63) == 0 && off != 0u) atomicAdd(bad, off);
 }
 
+// The same conversion for a rate schedule (lbsim_set_rate_schedule): B * P rows.  Element
+// (b, phase, s) of either input is in[b * row_stride + phase * phase_stride (+ s)]: the caller's
+// [B, P] / [B, P, S] arrays, one shared schedule (row stride 0), or per-env rates held constant
+// over the phases (phase stride 0).  out: tables of N = B * P rows, row b * P + phase.
+__global__ void __launch_bounds__(256)
+    rate_table_kernel(const float* arr_in, int64_t arr_row, int64_t arr_phase, const float* srv_in,
+                      int64_t srv_row, int64_t srv_phase, int B, int P, int S, EnvRates out,
+                      uint32_t* bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t off = 0u;
+  if (i < (int64_t)B * P * S) {
+    const int64_t r = i / S, b = r / P;
+    const float mu = srv_in[b * srv_row + (r - b * P) * srv_phase + (i - r * S)];
+    off += (!(mu >= 1.0f) || !(mu <= 1.0e7f)) ? 1u : 0u;
+    out.server[i] = mu;
+    out.scale[i] = (float)(1e6 / (double)mu);
+  }
+  if (i < (int64_t)B * P) {
+    const int64_t b = i / P;
+    const float r = arr_in[b * arr_row + (i - b * P) * arr_phase];
+    off += (!(r >= 0.1f) || !(r <= 1.0e6f)) ? 1u : 0u;
+    out.arrival[i] = r;
+    out.gap[i] = (float)(1e6 / (double)r);
+  }
+  for (int d = 32; d > 0; d >>= 1) off += __shfl_xor(off, d, 64);
+  if ((threadIdx.x & 63) == 0 && off != 0u) atomicAdd(bad, off);
+}
+
+// The phase of a rate schedule at episode step k (k / H, cyclic or clamped): the rule that
+// marllb_amd.randomize.schedule_phase states on the host.  P >= 1, H >= 1.
+__device__ __forceinline__ uint32_t sched_phase(int32_t k, uint32_t P, uint32_t H, bool wrap) {
+  const uint32_t j = (uint32_t)(k > 0 ? k : 0) / H;
+  return wrap ? j % P : (j < P ? j : P - 1u);
+}
+
+// The schedule's gather, one thread per (env, server): row b * P + phase of the [B, P] table
+// `per_env` and of the [B, P, S] table `per_srv` into env_out[B] / srv_out[B, S], and the phase
+// into phase_out[B] (each output optional).  The phase of env b is that of its next step launch,
+// from k = ep_step[b], the steps it has completed in its episode: sched_phase(k), or 0 when that
+// launch resets the env instead (next-step auto-reset, k >= max_steps).  reset != 0: the launch is
+// a reset of the envs of `mask` (nullptr: all), which runs at phase 0; the other envs are skipped.
+// It runs in front of every dynamics launch of a scheduled handle (sched_select: the tables' gap
+// and scale rows into the per-env arrays the dynamics kernels read) and behind
+// lbsim_get_env_rates / lbsim_rate_phase.  P <= 1 (no schedule, or one phase): phase 0, row b.
+__global__ void __launch_bounds__(256)
+    rate_gather_kernel(const int32_t* ep_step, const uint8_t* mask, int reset, int B, int S, int P,
+                       int H, int wrap, int max_steps, int next_reset, const float* per_env,
+                       const float* per_srv, float* env_out, float* srv_out, int32_t* phase_out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)B * S) return;
+  const int64_t b = i / S;
+  if (reset && mask != nullptr && mask[b] == 0) return;
+  uint32_t phase = 0u;
+  if (P > 1 && !reset) {
+    const int32_t k = ep_step[b];
+    if (!(next_reset && k >= max_steps))
+      phase = sched_phase(k, (uint32_t)P, (uint32_t)H, wrap != 0);
+  }
+  const int64_t row = P > 1 ? b * P + (int64_t)phase : b;
+  if (srv_out != nullptr) srv_out[i] = per_srv[row * S + (i - b * S)];
+  if (i - b * S == 0) {
+    if (env_out != nullptr) env_out[b] = per_env[row];
+    if (phase_out != nullptr) phase_out[b] = (int32_t)phase;
+  }
+}
+
 int launch_check(lbsim_t* h, const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, LBSIM_EDEVICE, "%s: %s", what, hipGetErrorString(e));
@@ -480,6 +553,84 @@ int env_rates_ensure(lbsim_t* h, hipStream_t s) {
   }
   env_rates_fill_defaults(h, s);
   return launch_check(h, "env_rates_kernel");
+}
+
+// ---- rate schedules (lbsim_set_rate_schedule).  A block for P phases holds, in
+// floats, with N = B * P rows: the live tables arrival[N], server[N*S], gap[N], scale[N*S] (row
+// b * P + phase), their staging copies, base[B + B*S] (the per-env rates in force before a call,
+// the source of a NULL argument), cur_gap[B] and cur_scale[B*S] (each env's row of gap / scale at
+// the phase of the launch in progress: what DevState::env_gap / env_scale point to, written by
+// sched_select), and the offender count (one u32).
+size_t sched_floats(const lbsim_t* h, int P) {
+  const size_t B = (size_t)h->B, N = B * (size_t)P, S = (size_t)h->S;
+  return 4 * (N + N * S) + 2 * (B + B * S);
+}
+EnvRates sched_live(const lbsim_t* h, float* buf, int P) {
+  const size_t N = (size_t)h->B * (size_t)P;
+  return env_rates_at(buf, N, N * h->S);
+}
+EnvRates sched_staging(const lbsim_t* h, float* buf, int P) {
+  const size_t N = (size_t)h->B * (size_t)P;
+  return env_rates_at(buf + 2 * (N + N * h->S), N, N * h->S);
+}
+float* sched_base(const lbsim_t* h, float* buf, int P) {
+  const size_t N = (size_t)h->B * (size_t)P;
+  return buf + 4 * (N + N * h->S);
+}
+float* sched_cur(const lbsim_t* h, float* buf, int P) {  // cur_gap, then cur_scale
+  return sched_base(h, buf, P) + (size_t)h->B + (size_t)h->B * h->S;
+}
+uint32_t* sched_bad(const lbsim_t* h, float* buf, int P) {
+  return reinterpret_cast<uint32_t*>(buf + sched_floats(h, P));
+}
+unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
+
+// The rates each env's next step launch will use (and / or its phase), on stream s: the phase's
+// row of a schedule's tables, else the per-env arrays (the config's rates when none are set).
+int rates_in_force(lbsim_t* h, float* arr_out, float* srv_out, int32_t* phase_out, hipStream_t s) {
+  const SimParams& p = h->prm;
+  EnvRates src{};
+  if (arr_out != nullptr || srv_out != nullptr) {
+    if (h->sched_P > 0) {
+      src = sched_live(h, h->sched_buf, h->sched_P);
+    } else {
+      const int rc = env_rates_ensure(h, s);
+      if (rc != LBSIM_OK) return rc;
+      src = env_rates_live(h);
+    }
+  }
+  hipLaunchKernelGGL(rate_gather_kernel, dim3(blocks256((size_t)h->B * h->S)), dim3(256), 0, s,
+                     h->st.ep_step, (const uint8_t*)nullptr, 0, h->B, h->S, h->sched_P, h->sched_H,
+                     h->sched_wrap, p.max_steps, p.next_reset, src.arrival, src.server, arr_out,
+                     srv_out, phase_out);
+  return launch_check(h, "rate_gather_kernel");
+}
+
+// In front of a dynamics launch of a scheduled handle (a step, or a reset of the envs of `mask`):
+// each env's gap and scale rows at the launch's phase into the per-env arrays the dynamics
+// kernels read.  One small launch on the step's stream, no allocation, no synchronisation; a
+// handle without a schedule launches nothing.  Not in the launch log or the profiler's classes:
+// those describe the step's own kernels.
+int sched_select(lbsim_t* h, const uint8_t* mask, int mode, hipStream_t s) {
+  if (h->sched_P == 0) return LBSIM_OK;
+  const SimParams& p = h->prm;
+  const EnvRates live = sched_live(h, h->sched_buf, h->sched_P);
+  float* const cur = sched_cur(h, h->sched_buf, h->sched_P);
+  hipLaunchKernelGGL(rate_gather_kernel, dim3(blocks256((size_t)h->B * h->S)), dim3(256), 0, s,
+                     h->st.ep_step, mask, mode == kModeReset ? 1 : 0, h->B, h->S, h->sched_P,
+                     h->sched_H, h->sched_wrap, p.max_steps, p.next_reset, live.gap, live.scale,
+                     cur, cur + h->B, (int32_t*)nullptr);
+  return launch_check(h, "rate_gather_kernel");
+}
+
+// Drops the schedule in force (if any): the kernels go back to the per-env arrays that were in
+// force before it, or to the config's shared rates.  The tables stay allocated.
+void sched_drop(lbsim_t* h) {
+  if (h->sched_P == 0) return;
+  h->sched_P = h->sched_H = h->sched_wrap = 0;
+  const EnvRates live = h->rates_on ? env_rates_live(h) : EnvRates{};
+  h->st.env_gap = live.gap;
+  h->st.env_scale = live.scale;
 }
 
 // Brackets one launch with profiler events when profiling is on (class: see lbsim.h).
@@ -743,6 +894,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->trace_buf) (void)hipFree(h->trace_buf);
     if (h->stats_buf) (void)hipFree(h->stats_buf);
     if (h->rates_buf) (void)hipFree(h->rates_buf);
+    if (h->sched_buf) (void)hipFree(h->sched_buf);
     if (h->flow_buf) (void)hipFree(h->flow_buf);
     for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
   }
@@ -789,7 +941,9 @@ int lbsim_reset_ex(lbsim_t* h, const uint8_t* env_mask, const lbsim_step_outputs
   LaunchLog log(h, 1);
   const hipStream_t s = (hipStream_t)stream;
   h->reset_seen = true;
-  int rc = launch_dynamics(h, nullptr, 0, nullptr, env_mask, kModeReset, s);
+  int rc = sched_select(h, env_mask, kModeReset, s);  // a rate schedule: a reset runs at phase 0
+  if (rc != LBSIM_OK) return rc;
+  rc = launch_dynamics(h, nullptr, 0, nullptr, env_mask, kModeReset, s);
   if (rc != LBSIM_OK) return rc;
   const ObsOutputs o = obs_outputs(out, true);
   rc = launch_observe(h, o, env_mask, kModeReset, s);
@@ -833,6 +987,8 @@ int lbsim_step_ex(lbsim_t* h, const void* action, int action_dtype,
   LaunchLog log(h, 0);
   const hipStream_t s = (hipStream_t)stream;
   const ObsOutputs o = obs_outputs(out, false);
+  if (sched_select(h, nullptr, kModeStep, s) != LBSIM_OK)  // a rate schedule: each env's phase
+    return LBSIM_EDEVICE;
   if (h->plan.form == kStepWave) {
     ProfScope ps(h, s, 4);
     launch_step_wave(ctx(h), action, action_dtype, out->assign_count, o, s);
@@ -957,6 +1113,7 @@ int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* serv
   if (nbad != 0u)  // the live arrays are untouched: the previous rates stay in force
     return fail(h, LBSIM_EINVAL, "per-env rates: %u value(s) out of range (arrival_rate must be in "
                                  "[0.1, 1e6] flows/s, server_rate in [1, 1e7]; NaN rejected)", nbad);
+  sched_drop(h);  // (a scheduled handle: back to its per-env arrays first)
   bool ok = true;
   if (arrival_rate != nullptr) {
     ok &= hipMemcpyAsync(live.arrival, stg.arrival, B * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
@@ -969,11 +1126,14 @@ int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* serv
   if (!ok) return fail(h, LBSIM_EDEVICE, "per-env rates: device copy failed");
   h->st.env_gap = live.gap;
   h->st.env_scale = live.scale;
+  h->rates_on = true;
   return LBSIM_OK;
 }
 
 int lbsim_clear_env_rates(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  sched_drop(h);
+  h->rates_on = false;
   h->st.env_gap = nullptr;
   h->st.env_scale = nullptr;
   if (h->rates_buf == nullptr) return LBSIM_OK;
@@ -994,6 +1154,8 @@ int lbsim_get_env_rates(lbsim_t* h, float* arrival_rate_out, float* server_rate_
   if (arrival_rate_out == nullptr && server_rate_out == nullptr) return LBSIM_OK;
   DeviceGuard g(h->device);
   const hipStream_t s = (hipStream_t)stream;
+  if (h->sched_P > 0)  // a schedule: each env's rates at the phase of its next step
+    return rates_in_force(h, arrival_rate_out, server_rate_out, nullptr, s);
   const int rc = env_rates_ensure(h, s);
   if (rc != LBSIM_OK) return rc;
   const size_t B = (size_t)h->B, BS = B * h->S;
@@ -1004,6 +1166,126 @@ int lbsim_get_env_rates(lbsim_t* h, float* arrival_rate_out, float* server_rate_
   if (server_rate_out != nullptr)
     ok &= hipMemcpyAsync(server_rate_out, live.server, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
   return ok ? LBSIM_OK : fail(h, LBSIM_EDEVICE, "per-env rates: device copy failed");
+}
+
+int lbsim_set_rate_schedule(lbsim_t* h, const float* arrival_rate, const float* server_rate,
+                            int32_t rows, int32_t phases, int32_t steps_per_phase, int32_t wrap,
+                            void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (phases < 1 || phases > 4096)
+    return fail(h, LBSIM_EINVAL, "rate schedule: phases must be in [1, 4096] (got %d)", phases);
+  if (steps_per_phase < 1)
+    return fail(h, LBSIM_EINVAL, "rate schedule: steps_per_phase must be >= 1 (got %d)",
+                steps_per_phase);
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "rate schedule: rows must be 1 or num_envs = %d (got %d)", h->B,
+                rows);
+  if (arrival_rate != nullptr && h->prm.lf_thr != 0u)
+    return fail(h, LBSIM_ENOTSUP, "an arrival schedule on a lost-FIN handle (lost_fin_prob > 0): "
+                                  "the bucket-wait mean and the 32-bit guess bound depend on the "
+                                  "arrival rate (server schedules are allowed)");
+  if (arrival_rate != nullptr && h->prm.trace)
+    return fail(h, LBSIM_ENOTSUP, "an arrival schedule on a TRACE handle: the trace sets the "
+                                  "arrival rate (server schedules are allowed)");
+  const int P = phases, S = h->S;
+  const size_t B = (size_t)h->B, N = B * (size_t)P, NS = N * (size_t)S;
+  if (NS > (size_t)INT32_MAX)
+    return fail(h, LBSIM_ENOMEM, "rate schedule: num_envs * phases * num_servers = %zu exceeds "
+                                 "2^31 - 1 table elements", NS);
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  // the tables: allocated by the first call for this P, rewritten in place by later ones
+  float* buf = h->sched_buf;
+  const bool fresh = buf == nullptr || h->sched_alloc_P != P;
+  if (fresh) {
+    const size_t bytes = sched_floats(h, P) * sizeof(float) + sizeof(uint32_t);
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess)
+      return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", bytes);
+    buf = (float*)p;
+  }
+  auto give_up = [&](int code, const char* what) {
+    if (fresh) (void)hipFree(buf);  // (waits for the device)
+    return fail(h, code, "rate schedule: %s", what);
+  };
+  // the per-env rates in force before this call (of the old schedule's tables, when there is
+  // one): what a NULL argument holds constant over the phases
+  float* const base = sched_base(h, buf, P);
+  int rc = rates_in_force(h, base, base + B, nullptr, s);
+  if (rc != LBSIM_OK) {
+    if (fresh) (void)hipFree(buf);
+    return rc;
+  }
+  const EnvRates live = sched_live(h, buf, P), stg = sched_staging(h, buf, P);
+  uint32_t* const bad = sched_bad(h, buf, P);
+  if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess)
+    return give_up(LBSIM_EDEVICE, "hipMemsetAsync failed");
+  const int64_t per_row = rows == 1 ? 0 : 1;  // one shared schedule: every env reads row 0
+  const float* const arr_in = arrival_rate != nullptr ? arrival_rate : base;
+  const float* const srv_in = server_rate != nullptr ? server_rate : base + B;
+  hipLaunchKernelGGL(rate_table_kernel, dim3(blocks256(NS)), dim3(256), 0, s, arr_in,
+                     arrival_rate != nullptr ? per_row * P : (int64_t)1,
+                     (int64_t)(arrival_rate != nullptr ? 1 : 0), srv_in,
+                     server_rate != nullptr ? per_row * P * S : (int64_t)S,
+                     (int64_t)(server_rate != nullptr ? S : 0), h->B, P, S, stg, bad);
+  if (launch_check(h, "rate_table_kernel") != LBSIM_OK) {
+    if (fresh) (void)hipFree(buf);
+    return LBSIM_EDEVICE;
+  }
+  uint32_t nbad = 0;
+  if (hipMemcpyAsync(&nbad, bad, sizeof(nbad), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return give_up(LBSIM_EDEVICE, "conversion failed");
+  if (nbad != 0u) {  // nothing live was touched: the previous schedule or rates stay in force
+    if (fresh) (void)hipFree(buf);
+    return fail(h, LBSIM_EINVAL, "rate schedule: %u value(s) out of range (arrival_rate must be in "
+                                 "[0.1, 1e6] flows/s, server_rate in [1, 1e7]; NaN rejected)", nbad);
+  }
+  // staging over the live tables (the two halves are contiguous: one copy)
+  if (hipMemcpyAsync(live.arrival, stg.arrival, 2 * (N + NS) * sizeof(float),
+                     hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return give_up(LBSIM_EDEVICE, "device copy failed");
+  if (fresh) {
+    if (h->sched_buf != nullptr) (void)hipFree(h->sched_buf);  // (waits for the device)
+    h->sched_buf = buf;
+    h->sched_alloc_P = P;
+  }
+  // the dynamics kernels read the per-env arrays that sched_select fills before every launch
+  float* const cur = sched_cur(h, buf, P);
+  h->st.env_gap = cur;
+  h->st.env_scale = cur + B;
+  h->sched_P = P;
+  h->sched_H = steps_per_phase;
+  h->sched_wrap = wrap != 0 ? 1 : 0;
+  return LBSIM_OK;
+}
+
+int lbsim_clear_rate_schedule(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  sched_drop(h);
+  if (h->sched_buf != nullptr) {
+    // a step captured into a graph while the schedule was set keeps reading the tables: they take
+    // the config's rates in every phase (no stream argument: the whole device is waited for)
+    DeviceGuard g(h->device);
+    int rc = env_rates_ensure(h, nullptr);
+    if (rc != LBSIM_OK) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) return fail(h, LBSIM_EDEVICE, "sync failed");
+    const float* def = env_rates_defaults(h);
+    const int P = h->sched_alloc_P;
+    hipLaunchKernelGGL(rate_table_kernel, dim3(blocks256((size_t)h->B * P * h->S)), dim3(256), 0,
+                       nullptr, def, (int64_t)0, (int64_t)0, def + 1, (int64_t)0, (int64_t)0, h->B,
+                       P, h->S, sched_live(h, h->sched_buf, P), sched_bad(h, h->sched_buf, P));
+    rc = launch_check(h, "rate_table_kernel");
+    if (rc != LBSIM_OK) return rc;
+  }
+  return lbsim_clear_env_rates(h);
+}
+
+int lbsim_rate_phase(lbsim_t* h, int32_t* phase_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (phase_out == nullptr) return LBSIM_OK;
+  DeviceGuard g(h->device);
+  return rates_in_force(h, nullptr, nullptr, phase_out, (hipStream_t)stream);
 }
 
 int lbsim_flow_stats_enable(lbsim_t* h) {

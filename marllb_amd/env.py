@@ -326,6 +326,31 @@ class Handle:
             self.h, ctypes.c_void_p(mask.data_ptr() if mask is not None else None),
             ctypes.c_void_p(self._stream())))
 
+    def set_rate_schedule(self, arrival=None, server=None, *, rows: int, phases: int,
+                          steps_per_phase: int = 1, wrap: bool = True) -> None:
+        """A rate schedule (lbsim_set_rate_schedule): arrival (rows, P) and / or server
+        (rows, P, S) f32 contiguous tensors on the handle's device, flows/s, rows = 1 or B; None
+        keeps that quantity's rates in force, constant over the phases."""
+        self.check(self.lib.lbsim_set_rate_schedule(
+            self.h, ctypes.c_void_p(arrival.data_ptr() if arrival is not None else None),
+            ctypes.c_void_p(server.data_ptr() if server is not None else None),
+            int(rows), int(phases), int(steps_per_phase), 1 if wrap else 0,
+            ctypes.c_void_p(self._stream())))
+
+    def clear_rate_schedule(self) -> None:
+        """Drop the schedule, back to the config's shared rates (lbsim_clear_rate_schedule)."""
+        self.check(self.lib.lbsim_clear_rate_schedule(self.h))
+
+    def rate_phase(self):
+        """(B,) int32 device tensor: the phase each env's next step launch will use
+        (lbsim_rate_phase); zeros without a schedule."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        out = torch.empty(int(self.cfg.num_envs), dtype=torch.int32, device=dev)
+        self.check(self.lib.lbsim_rate_phase(self.h, ctypes.c_void_p(out.data_ptr()),
+                                             ctypes.c_void_p(self._stream())))
+        return out
+
     def lost_fin_overflow(self) -> np.ndarray:
         """Per env (B,) uint32: the lost-FIN guesses dropped at a full pending ring this episode
         (the snapshot's last section, lf_over); zeros on a handle without lost-FIN."""
@@ -641,8 +666,70 @@ class VecLoadBalanceEnv:
 
     @property
     def rates(self):
-        """(arrival (B,), server (B, S)) f32 device tensors: the rates in force."""
+        """(arrival (B,), server (B, S)) f32 device tensors: the rates in force (with a rate
+        schedule: those each env's next step will use)."""
         return self.handle.env_rates()
+
+    def _schedule_arg(self, x, tail, name):
+        """A schedule argument as (rows, contiguous f32 tensor (rows, P) + tail) on the env's
+        device: x is (P,) + tail for one shared schedule or (B, P) + tail."""
+        torch = _torch()
+        t = torch.as_tensor(x)
+        shared = t.dim() == 1 + len(tail)
+        if not shared and t.dim() != 2 + len(tail):
+            raise ValueError(f"{name}: expected (P,) + {tail} or (B, P) + {tail}, got "
+                             f"{tuple(t.shape)}")
+        if shared:
+            t = t.unsqueeze(0)
+        if tuple(t.shape[2:]) != tail or t.shape[1] < 1 or (
+                not shared and t.shape[0] != self.num_envs):
+            raise ValueError(f"{name}: expected (P,) + {tail} or ({self.num_envs}, P) + {tail}, "
+                             f"got {tuple(torch.as_tensor(x).shape)}")
+        return t.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def set_rate_schedule(self, arrival=None, server=None, *, steps_per_phase: int = 1,
+                          wrap: bool = True) -> None:
+        """A rate schedule for non-stationary workloads: P phases, each held for steps_per_phase
+        agent steps, cyclic (wrap) or clamped at the last phase.  arrival is (P,) for one schedule
+        shared by every env or (B, P); server is (P, S) or (B, P, S); flows/s, tensors or arrays
+        on any device (cast to f32).  None keeps that quantity's rates in force (per-env or the
+        config's), constant over the phases.
+        An env that has completed k steps of its episode runs its next step at phase
+        (k // steps_per_phase) % P, or min(k // steps_per_phase, P - 1) when clamped
+        (marllb_amd.randomize.schedule_phase); a reset (warm-up and auto-reset included) runs at
+        phase 0.  A phase change acts as a mid-run set_rates: the arrival already drawn keeps its
+        time and work, every later gap and service time uses the new phase.  Ranges, ValueError
+        and the lost-FIN / trace rule for arrival are set_rates's.  Not part of get_state() (the
+        episode step is).  graph_mode: later calls with the same P rewrite the tables in place
+        and replays see them; a new P, steps_per_phase or wrap needs a new capture.  set_rates /
+        clear_rates drop the schedule.  (marllb_amd.randomize.diurnal_schedule and burst_schedule
+        draw such tables.)"""
+        S = self.num_servers
+        a = self._schedule_arg(arrival, (), "arrival") if arrival is not None else None
+        m = self._schedule_arg(server, (S,), "server") if server is not None else None
+        if a is None and m is None:
+            raise ValueError("set_rate_schedule: give arrival and / or server")
+        if a is not None and m is not None and a.shape[1] != m.shape[1]:
+            raise ValueError(f"set_rate_schedule: arrival has {a.shape[1]} phases, server "
+                             f"{m.shape[1]}")
+        if a is not None and m is not None and a.shape[0] != m.shape[0]:
+            # one shared, one per env: expand the shared one
+            B = self.num_envs
+            a = a.expand(B, *a.shape[1:]).contiguous()
+            m = m.expand(B, *m.shape[1:]).contiguous()
+        first = a if a is not None else m
+        self.handle.set_rate_schedule(a, m, rows=int(first.shape[0]), phases=int(first.shape[1]),
+                                      steps_per_phase=steps_per_phase, wrap=wrap)
+
+    def clear_rate_schedule(self) -> None:
+        """Drop the schedule: back to the config's shared arrival_rate / server_rates."""
+        self.handle.clear_rate_schedule()
+
+    @property
+    def rate_phase(self):
+        """(B,) int32 device tensor: the schedule phase each env's next step will use (zeros
+        without a schedule)."""
+        return self.handle.rate_phase()
 
     def flow_stats(self, per_server: bool = False, hist: bool = False) -> Dict[str, Any]:
         """The exact flow statistics since the last clear, as device tensors of shape (B,) or,

@@ -235,6 +235,19 @@ class VecMultiAgentLoadBalanceEnv:
     def rates(self):
         return self.vec.rates
 
+    def set_rate_schedule(self, arrival=None, server=None, *, steps_per_phase: int = 1,
+                          wrap: bool = True) -> None:
+        """A rate schedule, (P,) / (P, S) shared or (B, P) / (B, P, S):
+        VecLoadBalanceEnv.set_rate_schedule."""
+        self.vec.set_rate_schedule(arrival, server, steps_per_phase=steps_per_phase, wrap=wrap)
+
+    def clear_rate_schedule(self) -> None:
+        self.vec.clear_rate_schedule()
+
+    @property
+    def rate_phase(self):
+        return self.vec.rate_phase
+
     def flow_stats(self, per_server: bool = False, hist: bool = False):
         """Exact flow statistics of an env made with flow_stats=True: VecLoadBalanceEnv.flow_stats."""
         return self.vec.flow_stats(per_server, hist)

@@ -2,11 +2,15 @@
 
 sample_rates draws one arrival rate and one set of server rates per env, so one handle trains a
 policy across light, heavy and overloaded clusters with fast, slow and heterogeneous servers.
+diurnal_schedule and burst_schedule draw per-env arrival schedules whose load moves inside an
+episode (VecLoadBalanceEnv.set_rate_schedule); schedule_phase states the phase rule.
 Pure torch; deterministic for a seeded generator.
 """
 from __future__ import annotations
 
 import math
+
+import numpy as np
 
 
 def sample_rates(num_envs: int, num_servers: int, *, rate=(100.0, 1000.0), load=(0.3, 1.2),
@@ -40,3 +44,84 @@ def sample_rates(num_envs: int, num_servers: int, *, rate=(100.0, 1000.0), load=
     server = (arrival / rho).unsqueeze(1) * skew / skew.sum(dim=1, keepdim=True)
     return (arrival.to(device=device, dtype=torch.float32),
             server.to(device=device, dtype=torch.float32))
+
+
+# ---- rate schedules (VecLoadBalanceEnv.set_rate_schedule): non-stationary workloads
+
+ARRIVAL_RANGE = (0.1, 1.0e6)  # flows/s, make_config's range for arrival_rate
+
+
+def schedule_phase(k, phases: int, steps_per_phase: int = 1, wrap: bool = True):
+    """The phase a step runs at when the env has completed k steps of its episode: with
+    j = k // steps_per_phase, j % phases when cyclic (wrap), else min(j, phases - 1).  k: an int,
+    a numpy array or a torch tensor (k < 0 counts as 0).  The host statement of the rule the
+    dynamics kernels apply per env; a reset (warm-up included) always runs at phase 0."""
+    P, H = int(phases), int(steps_per_phase)
+    if P < 1 or H < 1:
+        raise ValueError(f"need phases >= 1 and steps_per_phase >= 1 (got {phases}, "
+                         f"{steps_per_phase})")
+    if isinstance(k, (int, np.integer)):
+        j = max(int(k), 0) // H
+        return j % P if wrap else min(j, P - 1)
+    if isinstance(k, np.ndarray):
+        j = np.maximum(k.astype(np.int64), 0) // H
+        return j % P if wrap else np.minimum(j, P - 1)
+    j = k.long().clamp(min=0) // H
+    return j % P if wrap else j.clamp(max=P - 1)
+
+
+def _arrival_rows(arrival, generator):
+    import torch
+
+    gdev = generator.device if generator is not None else torch.device("cpu")
+    a = torch.as_tensor(arrival, dtype=torch.float64).reshape(-1).to(gdev)
+    if a.numel() < 1 or not bool(((a >= ARRIVAL_RANGE[0]) & (a <= ARRIVAL_RANGE[1])).all()):
+        raise ValueError(f"arrival: need (B,) rates in [{ARRIVAL_RANGE[0]}, {ARRIVAL_RANGE[1]}]")
+    return a, gdev
+
+
+def diurnal_schedule(arrival, phases: int, *, amplitude=(0.2, 0.8), generator=None, device=None):
+    """-> arrival schedule (B, phases) float32, flows/s: a day of rising and falling load,
+    arrival[b] * (1 + a_b * sin(2 pi (j / phases + phi_b))) for phase j, with each env's relative
+    amplitude a_b uniform in amplitude = (lo, hi), 0 <= lo <= hi < 1, and its phase offset phi_b
+    uniform in [0, 1).  arrival: (B,) base rates (a scalar: one env).  Clamped to make_config's
+    arrival range; deterministic for a seeded generator."""
+    import torch
+
+    P = int(phases)
+    lo, hi = float(amplitude[0]), float(amplitude[1])
+    if P < 1 or not (0.0 <= lo <= hi < 1.0):
+        raise ValueError(f"need phases >= 1 and 0 <= lo <= hi < 1 (got {phases}, {amplitude})")
+    a, gdev = _arrival_rows(arrival, generator)
+    B = a.numel()
+    amp = lo + (hi - lo) * torch.rand(B, generator=generator, device=gdev, dtype=torch.float64)
+    phi = torch.rand(B, generator=generator, device=gdev, dtype=torch.float64)
+    j = torch.arange(P, device=gdev, dtype=torch.float64) / P
+    sched = a[:, None] * (1.0 + amp[:, None] * torch.sin(2.0 * math.pi * (j[None, :] + phi[:, None])))
+    return sched.clamp(*ARRIVAL_RANGE).to(device=device, dtype=torch.float32)
+
+
+def burst_schedule(arrival, phases: int, *, factor: float = 4.0, p_on: float = 0.1,
+                   p_off: float = 0.5, generator=None, device=None):
+    """-> arrival schedule (B, phases) float32, flows/s: bursts from a two-state Markov chain per
+    env, sampled once here.  Every env starts calm (phase 0, the phase of a reset); a calm phase is
+    followed by a burst with probability p_on, a burst by a calm phase with probability p_off;
+    a burst phase runs at arrival[b] * factor, a calm one at arrival[b].  Clamped to make_config's
+    arrival range; deterministic for a seeded generator."""
+    import torch
+
+    P = int(phases)
+    if P < 1 or not (float(factor) > 0.0 and math.isfinite(float(factor))):
+        raise ValueError(f"need phases >= 1 and a finite factor > 0 (got {phases}, {factor})")
+    for name, v in (("p_on", p_on), ("p_off", p_off)):
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"{name}: a probability (got {v})")
+    a, gdev = _arrival_rows(arrival, generator)
+    B = a.numel()
+    u = torch.rand((B, P), generator=generator, device=gdev, dtype=torch.float64)
+    on = torch.zeros((B, P), dtype=torch.bool, device=gdev)
+    for j in range(1, P):
+        prev = on[:, j - 1]
+        on[:, j] = torch.where(prev, u[:, j] >= float(p_off), u[:, j] < float(p_on))
+    sched = a[:, None] * torch.where(on, float(factor), 1.0)
+    return sched.clamp(*ARRIVAL_RANGE).to(device=device, dtype=torch.float32)
