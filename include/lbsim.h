@@ -605,6 +605,36 @@ int lbsim_state_size(const lbsim_t* h, size_t* bytes_out);
 int lbsim_get_state(lbsim_t* h, void* host_buf, size_t bytes);
 int lbsim_set_state(lbsim_t* h, const void* host_buf, size_t bytes);
 
+/* ---- on-device snapshots: save, restore and fork env states ----
+ * The same snapshot as above, in a caller-owned DEVICE buffer of lbsim_state_size bytes laid out
+ * exactly as lbsim_get_state lays out its host buffer (DESIGN.md §4, B envs): a buffer written by
+ * lbsim_state_save of all envs and copied to the host is byte-identical to lbsim_get_state at the
+ * same point.  Both calls are one kernel launch on `stream`: asynchronous, no allocation, no
+ * synchronisation, no host copy, so both can be captured into a hipGraph (the buffer and index
+ * pointers are then part of the capture; their contents are read at every replay).
+ * lbsim_state_save: copies the state of the envs with env_mask[b] != 0 (device u8[B]; NULL: all)
+ *   into dev_buf; bytes of envs outside the mask are left as they were.
+ * lbsim_state_load: env b takes the state that dev_buf holds for env src_env[b] (device
+ *   int32[B]); src_env NULL = identity, every env its own saved state.  An entry < 0 or >= B
+ *   leaves env b untouched: indices are never rejected on the device (a raise would need a host
+ *   synchronisation), out of range means "keep".  One source may feed many envs (a fork): they
+ *   share the queues, reservoirs and the one arrival already drawn, and since every later draw is
+ *   keyed by the env's own global id their futures are independent; an env loaded with its OWN
+ *   saved state replays exactly the arrivals, work, failures and reservoir draws it had from there.
+ *   A load with src_env == NULL marks the handle initialised, as lbsim_set_state does; with a
+ *   src_env the handle must have been reset or loaded before (LBSIM_EINVAL otherwise: the envs it
+ *   keeps would have no state).
+ * Errors: NULL handle or buffer, or a dev_buf that is not 16-byte aligned: LBSIM_EINVAL; bytes
+ *   other than lbsim_state_size: LBSIM_ESHAPE.
+ * Outside the snapshot, as for lbsim_get_state: the seed, the per-env rates and rate schedules,
+ *   the flow statistics and the trace.  A load leaves all of them as they are: a restored or
+ *   forked env runs at the rates (and schedule rows) of the SLOT it is loaded into, and its
+ *   slot's flow statistics go on counting. */
+int lbsim_state_save(lbsim_t* h, void* dev_buf, size_t bytes, const uint8_t* env_mask,
+                     void* stream);
+int lbsim_state_load(lbsim_t* h, const void* dev_buf, size_t bytes, const int32_t* src_env,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

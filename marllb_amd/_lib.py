@@ -196,6 +196,8 @@ _SIGNATURES = {
     "lbsim_state_size": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_size_t)]),
     "lbsim_get_state": (ctypes.c_int, [_P, _P, ctypes.c_size_t]),
     "lbsim_set_state": (ctypes.c_int, [_P, _P, ctypes.c_size_t]),
+    "lbsim_state_save": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
+    "lbsim_state_load": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
 }
 
 _lib = None

@@ -20,6 +20,7 @@
 #include "lbsim_internal.h"
 #include "lbsim_fused.h"
 #include "lbsim_nets.h"
+#include "lbsim_snapshot.h"
 #include "lbsim_stateless.h"
 #include "lbsim_vpp.h"
 
@@ -1713,6 +1714,64 @@ int lbsim_set_state(lbsim_t* h, const void* host_buf, size_t bytes) {
   h->initialised = true;
   h->reset_seen = true;
   return LBSIM_OK;
+}
+
+}  // extern "C"
+
+// ---- on-device snapshots (lbsim_state_save / lbsim_state_load)
+namespace {
+
+// One state_gather_kernel launch on `stream` over every section of the handle: no allocation, no
+// synchronisation, no copy (the section table travels by value in the kernel's arguments).
+int state_gather(lbsim_t* h, const char* who, void* dev_buf, size_t bytes, const uint8_t* mask,
+                 const int32_t* src_env, int dir, void* stream) {
+  if (h == nullptr) return fail(nullptr, LBSIM_EINVAL, "%s: handle is NULL", who);
+  if (dev_buf == nullptr) return fail(h, LBSIM_EINVAL, "%s: dev_buf is NULL", who);
+  if ((uintptr_t)dev_buf % 16u != 0)
+    return fail(h, LBSIM_EINVAL, "%s: dev_buf must be 16-byte aligned", who);
+  const std::vector<Section> secs = sections(h);
+  static_assert(kSnapMaxSections >= 27, "sections() lists up to 27 sections");
+  if (secs.size() > (size_t)kSnapMaxSections)
+    return fail(h, LBSIM_ENOTSUP, "%s: %zu state sections, the kernel's table holds %d", who,
+                secs.size(), kSnapMaxSections);
+  SnapInput in[kSnapMaxSections];
+  size_t need = 0;
+  for (size_t i = 0; i < secs.size(); ++i) {
+    in[i] = SnapInput{*secs[i].ptr, secs[i].bytes};
+    need += secs[i].bytes;
+  }
+  if (bytes != need)
+    return fail(h, LBSIM_ESHAPE, "%s: state buffer is %zu bytes, need %zu", who, bytes, need);
+  if (dir == kSnapLoad && src_env != nullptr && !h->initialised)
+    return fail(h, LBSIM_EINVAL, "%s with src_env needs a handle that was reset or loaded: the "
+                                 "envs it keeps have no state yet", who);
+  SnapTable t;
+  const uint64_t blocks = snap_table_build(t, in, (int)secs.size(), h->B, dev_buf);
+  DeviceGuard g(h->device);
+  const unsigned grid = (unsigned)std::min<uint64_t>(blocks, 1u << 20);
+  hipLaunchKernelGGL(state_gather_kernel, dim3(grid), dim3(kSnapBlock), 0, (hipStream_t)stream, t,
+                     static_cast<char*>(dev_buf), mask, src_env, dir, (int64_t)h->B);
+  const int rc = launch_check(h, "state_gather_kernel");
+  if (rc == LBSIM_OK && dir == kSnapLoad && src_env == nullptr) {
+    h->initialised = true;
+    h->reset_seen = true;
+  }
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lbsim_state_save(lbsim_t* h, void* dev_buf, size_t bytes, const uint8_t* env_mask,
+                     void* stream) {
+  return state_gather(h, "lbsim_state_save", dev_buf, bytes, env_mask, nullptr, kSnapSave, stream);
+}
+
+int lbsim_state_load(lbsim_t* h, const void* dev_buf, size_t bytes, const int32_t* src_env,
+                     void* stream) {
+  return state_gather(h, "lbsim_state_load", const_cast<void*>(dev_buf), bytes, nullptr, src_env,
+                      kSnapLoad, stream);
 }
 
 }  // extern "C"

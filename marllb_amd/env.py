@@ -244,6 +244,29 @@ class Handle:
     def load_state(self, data: bytes) -> None:
         self.check(self.lib.lbsim_set_state(self.h, data, len(data)))
 
+    def state_size(self) -> int:
+        n = ctypes.c_size_t()
+        self.check(self.lib.lbsim_state_size(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def state_save(self, buf, mask=None) -> None:
+        """The state of the envs with mask[b] set (a contiguous uint8 device tensor of B entries;
+        None: every env) into buf, a contiguous uint8 device tensor of state_size() bytes laid
+        out as state_bytes(); one kernel on the current stream (lbsim_state_save)."""
+        self.check(self.lib.lbsim_state_save(
+            self.h, ctypes.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size(),
+            ctypes.c_void_p(mask.data_ptr() if mask is not None else None),
+            ctypes.c_void_p(self._stream())))
+
+    def state_load(self, buf, src=None) -> None:
+        """Env b takes the state buf holds for env src[b] (a contiguous int32 device tensor of B
+        entries; None: its own; an entry outside [0, B) keeps env b as it is); one kernel on the
+        current stream (lbsim_state_load)."""
+        self.check(self.lib.lbsim_state_load(
+            self.h, ctypes.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size(),
+            ctypes.c_void_p(src.data_ptr() if src is not None else None),
+            ctypes.c_void_p(self._stream())))
+
     def set_trace(self, trace) -> None:
         """Copy a marllb_amd.trace.Trace to the device and install it (lbsim_set_trace)."""
         torch = _torch()
@@ -358,6 +381,23 @@ class Handle:
         if not self.cfg.lost_fin_prob > 0:
             return np.zeros(B, np.uint32)
         return np.frombuffer(self.state_bytes()[-4 * B:], dtype=np.uint32).copy()
+
+
+class DeviceSnapshot:
+    """A saved state of a VecLoadBalanceEnv, resident on its GPU (snapshot() / restore()).
+
+    state   (state_size,) uint8: the handle's state, laid out as get_state()
+    obs     (B, S, 11) f32: the observation batch the env had returned last
+    up_ret  (B,) f64 episode returns of feature_mode="upstream" (None otherwise)
+    host    the single-env facade's own bookkeeping (LoadBalanceEnv.snapshot), else None
+    Not saved, as for get_state(): the seed, per-env rates and rate schedules, the flow statistics
+    and the trace.
+    """
+
+    __slots__ = ("state", "obs", "up_ret", "host")
+
+    def __init__(self, state, obs, up_ret=None, host=None):
+        self.state, self.obs, self.up_ret, self.host = state, obs, up_ret, host
 
 
 class VecLoadBalanceEnv:
@@ -777,6 +817,108 @@ class VecLoadBalanceEnv:
         self._step_bound = self.cfg.max_steps  # unknown episode steps: keep auto-reset armed
         self._synced = False
 
+    def snapshot(self, mask=None, out: Optional[DeviceSnapshot] = None) -> DeviceSnapshot:
+        """Save the envs' states on the device (lbsim_state_save): the handle's state, the last
+        observation batch and, for feature_mode="upstream", the episode returns.  One kernel and
+        a copy or two on the current stream, no host synchronisation.
+        out: an earlier snapshot of this env to overwrite in place (its tensors are reused: the
+        form for loops and for graph_mode, where a captured restore(out) then follows the new
+        contents).  mask (bool / uint8, num_envs entries; needs out): only those envs' rows of
+        all three are refreshed, the others keep what out held.
+        What a snapshot does not hold is listed at DeviceSnapshot."""
+        torch = _torch()
+        if not self._reset_done or getattr(self, "_last_obs", None) is None:
+            raise RuntimeError("call reset() before snapshot()")
+        B = self.num_envs
+        upstream = self.feature_mode == "upstream"
+        if out is None:
+            if mask is not None:
+                raise ValueError("snapshot(mask=...) refreshes the masked envs of an existing "
+                                 "snapshot: pass it as out=")
+            out = DeviceSnapshot(
+                torch.empty(self.handle.state_size(), dtype=torch.uint8, device=self.device),
+                torch.empty_like(self._last_obs),
+                torch.zeros(B, dtype=torch.float64, device=self.device) if upstream else None)
+        m = None if mask is None else self._mask(mask)
+        self.handle.state_save(out.state, m)
+        ret = None
+        if upstream:
+            ret = self._up_ret if self._up_ret is not None else torch.zeros_like(out.up_ret)
+        if m is None:
+            out.obs.copy_(self._last_obs)
+            if upstream:
+                out.up_ret.copy_(ret)
+        else:
+            mb = m.bool()
+            out.obs.copy_(torch.where(mb.view(B, 1, 1), self._last_obs, out.obs))
+            if upstream:
+                out.up_ret.copy_(torch.where(mb, ret, out.up_ret))
+        return out
+
+    def restore(self, snap: DeviceSnapshot, mask=None, src=None):
+        """Put envs back into states saved by snapshot() (lbsim_state_load); returns the complete
+        observation batch, as a masked reset() does: restored rows hold the snapshot's
+        observation rows, the other rows the last observation.
+        mask (bool / uint8, num_envs entries): those envs go back to their own saved state.
+        src (integers, num_envs entries): env b takes the saved state of env src[b] -- a fork; an
+        entry that is negative or >= num_envs keeps env b as it is (indices are not checked on
+        the host: that would synchronise).  With both, mask wins where it is false.  Neither:
+        every env goes back to its own saved state.
+        An env restored into its own slot replays exactly the arrivals, work, failures and
+        reservoir draws it had from the saved state on (the randomness is keyed by the env's
+        global id and its saved counters): run policy A, restore, run policy B on the same flows.
+        An env restored into another slot shares the saved queues, reservoirs and the one arrival
+        already drawn, and draws everything after that with its own id: N copies of one state are
+        N independent futures.  Rates, schedules and flow statistics stay with the slot.
+        One kernel, no host synchronisation; in graph_mode every tensor involved is a buffer
+        allocated once (keep mask / src in tensors of your own that the replays read)."""
+        torch = _torch()
+        B = self.num_envs
+        upstream = self.feature_mode == "upstream"
+        if upstream and self._up_ret is None:
+            self._up_ret = torch.zeros(B, dtype=torch.float64, device=self.device)
+        if mask is None and src is None:
+            self.handle.state_load(snap.state)
+            obs = self._obs_buffer()
+            obs.copy_(snap.obs)
+            if upstream:
+                self._up_ret.copy_(snap.up_ret)
+        else:
+            if not self._reset_done or getattr(self, "_last_obs", None) is None:
+                raise RuntimeError("call reset() before restore() with a mask or src")
+            if src is None:
+                idx = torch.arange(B, dtype=torch.int32, device=self.device)
+            else:
+                idx = torch.as_tensor(src)
+                if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+                    raise ValueError(f"restore src must be an integer tensor, got {idx.dtype}")
+                if idx.numel() != B:
+                    raise ValueError(f"restore src must have num_envs={B} entries, got "
+                                     f"{idx.numel()}")
+                # clamped before the cast, so an index past int32 stays out of range
+                idx = idx.reshape(-1).to(self.device).clamp(-1, B).to(torch.int32)
+            if mask is not None:
+                idx = torch.where(self._mask(mask).bool(), idx, torch.full_like(idx, -1))
+            ibuf = self._buf("restore_src", (B,), torch.int32)
+            ibuf.copy_(idx)
+            self.handle.state_load(snap.state, ibuf)
+            ok = (ibuf >= 0) & (ibuf < B)
+            rows = ibuf.clamp(0, B - 1).long()
+            new = torch.where(ok.view(B, 1, 1), snap.obs.index_select(0, rows), self._last_obs)
+            if self.graph_mode:
+                obs = self._last_obs
+                obs.copy_(new)
+            else:
+                obs = new
+            if upstream:
+                self._up_ret.copy_(torch.where(ok, snap.up_ret.index_select(0, rows),
+                                               self._up_ret))
+        self._reset_done = True
+        self._step_bound = self.cfg.max_steps  # unknown episode steps: keep auto-reset armed
+        self._synced = False
+        self._last_obs = obs
+        return obs
+
     def close(self) -> None:
         self.handle.close()
 
@@ -860,6 +1002,7 @@ class LoadBalanceEnv:
             **sim_kwargs)
         self._io = None
         self._seq = 0
+        self._cur_obs = None  # (self._seq, obs) of the last reset / restore
         self._dw32 = None  # (discrete_weights as a tuple, the same as float32 values in a list)
         self._active_lut: Dict[bytes, List[int]] = {}
 
@@ -900,6 +1043,7 @@ class LoadBalanceEnv:
         """Reset the simulator; returns the (possibly normalised) first observation."""
         obs = self._vec.reset()[0].cpu().numpy()
         self._last_raw = obs
+        self._cur_obs = (self._seq, obs)  # snapshot(): the observation in force until a step
         if self._host_norm:
             obs = self._normalize_host(obs)
         return obs
@@ -1133,6 +1277,41 @@ class LoadBalanceEnv:
 
     def clear_flow_stats(self) -> None:
         self._flow_vec().clear_flow_stats()
+
+    # ---- on-device snapshots (VecLoadBalanceEnv.snapshot / restore of the one env)
+    def _snap_vec(self) -> "VecLoadBalanceEnv":
+        if self._vec is None or self.shm is not None:
+            raise RuntimeError("snapshots need the GPU simulator (not reference_plumbing / SHM)")
+        return self._vec
+
+    def snapshot(self, out: Optional[DeviceSnapshot] = None) -> DeviceSnapshot:
+        """Save the env's state on the device, with this facade's own episode bookkeeping
+        (step count, return, rewards); out: an earlier snapshot to overwrite."""
+        v = self._snap_vec()
+        snap = v.snapshot(out=out)
+        if self._cur_obs is not None and self._cur_obs[0] == self._seq:
+            obs = self._cur_obs[1]  # no step since the reset / restore that returned it
+        else:  # the last step's observation, still in the pinned output buffer
+            n = self.num_servers * NF
+            obs = self._io[1][:n].reshape(self.num_servers, NF).copy()
+        snap.obs.copy_(_torch().from_numpy(np.ascontiguousarray(obs))[None])
+        snap.host = {"current_step": self.current_step, "episode_return": self.episode_return,
+                     "episode_rewards": list(self.episode_rewards), "last_raw": self._last_raw}
+        return snap
+
+    def restore(self, snap: DeviceSnapshot) -> np.ndarray:
+        """Back to a state saved by snapshot(); returns the observation the env had returned
+        then.  The same actions from here give the same observations and rewards again."""
+        v = self._snap_vec()
+        if snap.host is None:
+            raise ValueError("restore() needs a snapshot taken by LoadBalanceEnv.snapshot()")
+        obs = v.restore(snap)[0].cpu().numpy()
+        self.current_step = snap.host["current_step"]
+        self.episode_return = snap.host["episode_return"]
+        self.episode_rewards = list(snap.host["episode_rewards"])
+        self._last_raw = snap.host["last_raw"]
+        self._cur_obs = (self._seq, obs)
+        return obs.copy()
 
     def render(self, mode: str = "human"):
         if mode == "human":
