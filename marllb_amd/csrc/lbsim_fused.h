@@ -12,7 +12,10 @@
 // leave LDS ([R][ld] f32, ld = 4 mod 64 so the MFMA operand reads are bank-conflict free), weights
 // stream from L2 in MFMA-fragment order, every GEMM is v_mfma_f32_16x16x4_f32 (exact f32 FMA
 // chain, the same numerics class as the fp32 hipBLASLt path it replaces: tested to 1e-5 against
-// the torch modules).  Per layer each wave accumulates its output tiles in registers, the
+// float64 copies of the torch modules on the host, and the noise and exploration draws against a
+// host Philox, at every staging branch, tile size and head / agent / mixer width the launchers
+// accept, tests/test_fused_policy_shapes.py; against the fp32 torch modules at the full shards,
+// tests/test_fused_policy.py).  Per layer each wave accumulates its output tiles in registers, the
 // workgroup barriers, then writes the activated tile back over its input (so one LDS buffer serves
 // every layer).
 //

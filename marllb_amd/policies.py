@@ -341,15 +341,25 @@ class FusedQMIXPolicy:
     mixer on the global state.  Reference widths: gru 64, hidden 128, embed 32, hypernet 64."""
 
     @staticmethod
-    def supported(agents, mixer: QMixer, n_actions: int) -> bool:
-        a0 = agents[0]
-        A, E, he = len(agents), mixer.mixing_embed_dim, mixer.hypernet_embed_dim
-        return (all(a.gru_dim == 64 and a.hidden_dim == 128 and a.obs_dim == a0.obs_dim
-                    for a in agents)
-                and 1 <= n_actions <= 16 and A <= 16 and a0.obs_dim <= 512
-                and mixer.state_dim <= 512 and E % 16 == 0 and he % 16 == 0
+    def widths_supported(A: int, obs_dim: int, state_dim: int, n_actions: int, E: int, he: int,
+                         gru_dim: int = 64, hidden_dim: int = 128) -> bool:
+        """The widths lbsim_qmix_policy_step accepts (its own checks, lbsim_api.hip)."""
+        return (gru_dim == 64 and hidden_dim == 128 and 1 <= n_actions <= 16 and 1 <= A <= 16
+                and 1 <= obs_dim <= 512 and 1 <= state_dim <= 512
+                and E >= 16 and E % 16 == 0 and he >= 16 and he % 16 == 0
                 and 3 * he + E <= 256 and A * E // 16 + E // 16 + 1 <= 16
-                and A * E + E + 16 <= 3 * he and next(mixer.parameters()).is_cuda)
+                and A * E + E + 16 <= 3 * he)
+
+    @staticmethod
+    def supported(agents, mixer: QMixer, n_actions: int) -> bool:
+        a0 = agents[0] if len(agents) else None
+        return (a0 is not None
+                and all((a.gru_dim, a.hidden_dim, a.obs_dim)
+                        == (a0.gru_dim, a0.hidden_dim, a0.obs_dim) for a in agents)
+                and FusedQMIXPolicy.widths_supported(
+                    len(agents), a0.obs_dim, mixer.state_dim, n_actions,
+                    mixer.mixing_embed_dim, mixer.hypernet_embed_dim, a0.gru_dim, a0.hidden_dim)
+                and next(mixer.parameters()).is_cuda)
 
     def __init__(self, agents, mixer: QMixer, n_actions: int = 3, epsilon: float = 0.05,
                  seed: int = 0, servers_per_agent: int = 1):
