@@ -495,6 +495,53 @@ int lbsim_set_rate_schedule(lbsim_t* h, const float* arrival_rate, const float* 
 int lbsim_clear_rate_schedule(lbsim_t* h);
 int lbsim_rate_phase(lbsim_t* h, int32_t* phase_out, void* stream);
 
+/* ---- trace banks (per-env trace selection and trace schedules) ----
+ * The TRACE counterpart of the two sections above.  One handle holds a bank of n_traces (T)
+ * traces, back to back in one device buffer: trace t is rows [row_begin[t], row_begin[t + 1]),
+ * R_t >= 1 of them.  Each env replays the trace its own id names: with env gid on trace t, the
+ * k-th arrival of its episode e reads bank row
+ *     row_begin[t] + ((gid * 7919 + (e - 1) * 1000003 + k) mod R_t),
+ * which is what a handle given trace t alone by lbsim_set_trace reads.
+ * lbsim_set_trace_bank replaces loading one of the reference's per-load files
+ * (data/trace/poisson_for_loop/rate_*.csv, the rows of src/client/replay_fork_io.py:95-121) per
+ * run: gap_us / work are DEVICE arrays of row_begin[n_traces] rows (lbsim_set_trace's columns),
+ * row_begin a HOST array of n_traces + 1 ascending offsets with row_begin[0] = 0.  1 <= T <= 4096,
+ * every R_t >= 1, fewer than 2^31 rows in all (LBSIM_EINVAL otherwise, and on a non-TRACE handle).
+ * lbsim_set_trace is the case T = 1.  Either call drops any selection or schedule: every env is
+ * back on trace 0.  A bank of the size (rows, T) of the one it replaces is rewritten in place; any
+ * other moves the buffer, and a captured graph needs a new capture.
+ * lbsim_set_trace_schedule replaces the reference's replay of one file per traffic level over a
+ * day (src/client/replay_fork_io.py:95-121 started once per data/trace/poisson_for_loop/rate_*.csv):
+ * trace_id [rows, P] int32 DEVICE, rows = 1 (every env the same schedule) or B, P phases each held
+ * for steps_per_phase agent steps, cyclic (wrap != 0) or clamped.  The phase rule and the reset
+ * rule are those of the rate schedules above, verbatim: phase (k / H) % P or min(k / H, P - 1)
+ * with k the env's episode step at the launch; phase 0 for lbsim_reset, its warm-up steps and the
+ * in-launch reset of a next_step_reset handle.  P = 1 is a constant per-env trace.  A change of
+ * trace between two launches keeps the arrival already drawn (its time and work), the arrival
+ * index and the episode; every later arrival reads the new trace at the row rule's index.
+ * The call waits on `stream`.  LBSIM_EINVAL: a non-TRACE handle, no trace set yet, P outside
+ * [1, 4096], steps_per_phase < 1, or an id outside [0, T) (the count in lbsim_last_error; the
+ * selection in force stays untouched).  LBSIM_ESHAPE: rows neither 1 nor B.  LBSIM_ENOTSUP: a
+ * lost-FIN handle (lost_fin_prob > 0: the bucket-wait mean is derived from the handle's one
+ * arrival rate); a bank whose envs all stay on trace 0 is allowed there.  A trace schedule and a
+ * server-rate schedule may be in force together, each with its own P, H and wrap.
+ * A handle with a selection launches one small kernel in front of each dynamics launch; the
+ * tables are allocated by the first call for a given P and rewritten in place by later calls with
+ * the same P, so a step captured into a hipGraph after the first call sees the new ids on replay.
+ * P, H and wrap are kernel arguments: a change of them, or dropping the schedule, needs a new
+ * capture.  lbsim_step / lbsim_reset gain no allocation and no synchronisation.  The selection is
+ * NOT part of the snapshot; the episode step is.
+ * lbsim_clear_trace_schedule: every env back to trace 0 (waits for the device; the tables stay
+ * allocated and take id 0).
+ * lbsim_env_trace: per env, the trace (trace_id_out[B]) and the phase (phase_out[B]) its next step
+ * launch will use, int32 DEVICE, either may be NULL; zeros on a handle without a selection. */
+int lbsim_set_trace_bank(lbsim_t* h, const uint32_t* gap_us, const float* work,
+                         const int64_t* row_begin, int n_traces, void* stream);
+int lbsim_set_trace_schedule(lbsim_t* h, const int32_t* trace_id, int rows, int P,
+                             int steps_per_phase, int wrap, void* stream);
+int lbsim_clear_trace_schedule(lbsim_t* h);
+int lbsim_env_trace(lbsim_t* h, int32_t* trace_id_out, int32_t* phase_out, void* stream);
+
 /*
  * Exact flow-completion-time statistics, opt-in per handle.  A handle with
  * them on counts every flow that completes during a STEP of an env, once, with its true

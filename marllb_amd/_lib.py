@@ -176,6 +176,11 @@ _SIGNATURES = {
                                                ctypes.c_int32, ctypes.c_int32, _P]),
     "lbsim_clear_rate_schedule": (ctypes.c_int, [_P]),
     "lbsim_rate_phase": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_set_trace_bank": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, _P]),
+    "lbsim_set_trace_schedule": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, _P]),
+    "lbsim_clear_trace_schedule": (ctypes.c_int, [_P]),
+    "lbsim_env_trace": (ctypes.c_int, [_P, _P, _P, _P]),
     "lbsim_flow_stats_enable": (ctypes.c_int, [_P]),
     "lbsim_flow_stats_get": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "lbsim_flow_stats_quantiles": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),

@@ -72,6 +72,16 @@ struct lbsim {
   StepPlan plan;  // which kernels a step / reset launches (lbsim_plan.h): made once, at create
   std::vector<void*> allocs;
   void* trace_buf = nullptr;  // gap_us[rows] then work[rows]
+  // the bank in trace_buf (lbsim_set_trace: one trace): its row offsets (T + 1; empty: no trace
+  // set), and their device copy as u32, made when a selection first needs it
+  std::vector<int64_t> bank_begin;
+  uint32_t* bank_begin_dev = nullptr;
+  // lbsim_set_trace_schedule: the selection's block for tsel_alloc_P phases (TraceSelBuf below),
+  // moved only by a call with another P, and the selection in force: tsel_P phases (0: none),
+  // each held for tsel_H steps, cyclic or clamped.
+  void* tsel_buf = nullptr;
+  int tsel_alloc_P = 0;
+  int tsel_P = 0, tsel_H = 0, tsel_wrap = 0;
   unsigned long long* stats_buf = nullptr;  // lbsim_step_stats sums (2 x u64)
   // lbsim_set_env_rates: one block, allocated by the first call and never moved (EnvRates below)
   float* rates_buf = nullptr;
@@ -450,6 +460,55 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// A trace schedule's ids (lbsim_set_trace_schedule) expanded to B rows: out[b * P + phase] =
+// in[b * row_stride + phase] (row stride 0: one shared schedule).  Ids outside [0, T) are counted
+// into *bad, as rate_table_kernel counts rates out of range.
+__global__ void __launch_bounds__(256)
+    trace_table_kernel(const int32_t* in, int64_t row_stride, int B, int P, int T, int32_t* out,
+                       uint32_t* bad) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t off = 0u;
+  if (i < (int64_t)B * P) {
+    const int64_t b = i / P;
+    const int32_t t = in[b * row_stride + (i - b * P)];
+    off = (t < 0 || t >= T) ? 1u : 0u;
+    out[i] = t;
+  }
+  for (int d = 32; d > 0; d >>= 1) off += __shfl_xor(off, d, 64);
+  if ((threadIdx.x & 63) == 0 && off != 0u) atomicAdd(bad, off);
+}
+
+// The trace selection's gather, one thread per env: the id at row b * P + phase of the [B, P]
+// table `ids` (nullptr, or P == 0: id 0), and its trace's descriptor {begin[t], begin[t + 1] -
+// begin[t]} into desc_out[b] (what env_trace(DevState) points to: one 8-byte vector store), the
+// id into id_out[b] and the phase into phase_out[b] (each output optional).  The phase is
+// rate_gather_kernel's: sched_phase of k = ep_step[b], or 0 when the env's next step launch resets
+// it instead (next-step auto-reset, k >= max_steps); reset != 0: a reset of the envs of `mask`
+// (nullptr: all) at phase 0, the other envs skipped.  It runs in front of every dynamics launch
+// of a handle with a selection (trace_select) and behind lbsim_env_trace.
+__global__ void __launch_bounds__(256)
+    trace_gather_kernel(const int32_t* ep_step, const uint8_t* mask, int reset, int B, int P, int H,
+                        int wrap, int max_steps, int next_reset, const int32_t* ids,
+                        const uint32_t* begin, uint2* desc_out, int32_t* id_out,
+                        int32_t* phase_out) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= (int64_t)B) return;
+  if (reset && mask != nullptr && mask[b] == 0) return;
+  uint32_t phase = 0u;
+  if (P > 1 && !reset) {
+    const int32_t k = ep_step[b];
+    if (!(next_reset && k >= max_steps))
+      phase = sched_phase(k, (uint32_t)P, (uint32_t)H, wrap != 0);
+  }
+  const int32_t t = (ids != nullptr && P > 0) ? ids[b * P + (int64_t)phase] : 0;
+  if (desc_out != nullptr) {
+    const uint32_t lo = begin[t];
+    desc_out[b] = make_uint2(lo, begin[t + 1] - lo);
+  }
+  if (id_out != nullptr) id_out[b] = t;
+  if (phase_out != nullptr) phase_out[b] = (int32_t)phase;
+}
+
 int launch_check(lbsim_t* h, const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, LBSIM_EDEVICE, "%s: %s", what, hipGetErrorString(e));
@@ -586,6 +645,36 @@ uint32_t* sched_bad(const lbsim_t* h, float* buf, int P) {
 }
 unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
 
+// The per-env arrays the dynamics kernels read.  A TRACE handle draws no gap: its env_gap word
+// carries the trace selection (env_trace(DevState)), which only lbsim_set_trace_schedule sets.
+void set_env_arrays(lbsim_t* h, const float* gap, const float* scale) {
+  if (!h->prm.trace) h->st.env_gap = gap;
+  h->st.env_scale = scale;
+}
+
+// ---- trace selection (lbsim_set_trace_schedule).  A block for P phases holds
+// cur[B] (uint2: each env's descriptor at the phase of the launch in progress, what
+// env_trace(DevState) points to, written by trace_select), the live ids [B * P] (row b * P +
+// phase), their staging copy, and the offender count (one u32).
+struct TraceSelBuf {
+  uint2* cur;
+  int32_t *live, *staging;
+  uint32_t* bad;
+};
+size_t trace_sel_bytes(const lbsim_t* h, int P) {
+  const size_t B = (size_t)h->B;
+  return B * sizeof(uint2) + 2 * B * (size_t)P * sizeof(int32_t) + sizeof(uint32_t);
+}
+TraceSelBuf trace_sel_at(const lbsim_t* h, void* buf, int P) {
+  const size_t B = (size_t)h->B, N = B * (size_t)P;
+  TraceSelBuf t;
+  t.cur = (uint2*)buf;
+  t.live = (int32_t*)(t.cur + B);
+  t.staging = t.live + N;
+  t.bad = (uint32_t*)(t.staging + N);
+  return t;
+}
+
 // The rates each env's next step launch will use (and / or its phase), on stream s: the phase's
 // row of a schedule's tables, else the per-env arrays (the config's rates when none are set).
 int rates_in_force(lbsim_t* h, float* arr_out, float* srv_out, int32_t* phase_out, hipStream_t s) {
@@ -630,8 +719,43 @@ void sched_drop(lbsim_t* h) {
   if (h->sched_P == 0) return;
   h->sched_P = h->sched_H = h->sched_wrap = 0;
   const EnvRates live = h->rates_on ? env_rates_live(h) : EnvRates{};
-  h->st.env_gap = live.gap;
-  h->st.env_scale = live.scale;
+  set_env_arrays(h, live.gap, live.scale);
+}
+
+// In front of a dynamics launch of a handle with a trace selection (a step, or a reset of the
+// envs of `mask`): each env's trace descriptor at the launch's phase into the array the TRACE
+// kernels read.  As sched_select: one small launch on the step's stream, no allocation, no
+// synchronisation, not in the launch log; a handle without a selection pays the one test.
+int trace_select(lbsim_t* h, const uint8_t* mask, int mode, hipStream_t s) {
+  if (h->tsel_P == 0) return LBSIM_OK;
+  const SimParams& p = h->prm;
+  const TraceSelBuf t = trace_sel_at(h, h->tsel_buf, h->tsel_P);
+  hipLaunchKernelGGL(trace_gather_kernel, dim3(blocks256((size_t)h->B)), dim3(256), 0, s,
+                     h->st.ep_step, mask, mode == kModeReset ? 1 : 0, h->B, h->tsel_P, h->tsel_H,
+                     h->tsel_wrap, p.max_steps, p.next_reset, t.live, h->bank_begin_dev, t.cur,
+                     (int32_t*)nullptr, (int32_t*)nullptr);
+  return launch_check(h, "trace_gather_kernel");
+}
+
+// The bank's row offsets to the device (u32: fewer than 2^31 rows), for trace_gather_kernel.
+// Off the step path: it waits for the copy.
+int bank_begin_upload(lbsim_t* h) {
+  const size_t n = h->bank_begin.size();
+  if (h->bank_begin_dev == nullptr && hipMalloc((void**)&h->bank_begin_dev, n * 4) != hipSuccess) {
+    h->bank_begin_dev = nullptr;
+    return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", n * 4);
+  }
+  std::vector<uint32_t> b32(h->bank_begin.begin(), h->bank_begin.end());
+  if (hipMemcpy(h->bank_begin_dev, b32.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "trace bank: upload of the row offsets failed");
+  return LBSIM_OK;
+}
+
+// Drops the trace selection in force (if any): every env replays trace 0 again.  The tables stay
+// allocated.
+void trace_sel_drop(lbsim_t* h) {
+  h->tsel_P = h->tsel_H = h->tsel_wrap = 0;
+  if (h->prm.trace) set_env_trace(h->st, nullptr);
 }
 
 // Brackets one launch with profiler events when profiling is on (class: see lbsim.h).
@@ -893,6 +1017,8 @@ int lbsim_destroy(lbsim_t* h) {
     DeviceGuard g(h->device);
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->trace_buf) (void)hipFree(h->trace_buf);
+    if (h->bank_begin_dev) (void)hipFree(h->bank_begin_dev);
+    if (h->tsel_buf) (void)hipFree(h->tsel_buf);
     if (h->stats_buf) (void)hipFree(h->stats_buf);
     if (h->rates_buf) (void)hipFree(h->rates_buf);
     if (h->sched_buf) (void)hipFree(h->sched_buf);
@@ -944,6 +1070,8 @@ int lbsim_reset_ex(lbsim_t* h, const uint8_t* env_mask, const lbsim_step_outputs
   h->reset_seen = true;
   int rc = sched_select(h, env_mask, kModeReset, s);  // a rate schedule: a reset runs at phase 0
   if (rc != LBSIM_OK) return rc;
+  rc = trace_select(h, env_mask, kModeReset, s);  // a trace schedule: the same
+  if (rc != LBSIM_OK) return rc;
   rc = launch_dynamics(h, nullptr, 0, nullptr, env_mask, kModeReset, s);
   if (rc != LBSIM_OK) return rc;
   const ObsOutputs o = obs_outputs(out, true);
@@ -989,6 +1117,8 @@ int lbsim_step_ex(lbsim_t* h, const void* action, int action_dtype,
   const hipStream_t s = (hipStream_t)stream;
   const ObsOutputs o = obs_outputs(out, false);
   if (sched_select(h, nullptr, kModeStep, s) != LBSIM_OK)  // a rate schedule: each env's phase
+    return LBSIM_EDEVICE;
+  if (trace_select(h, nullptr, kModeStep, s) != LBSIM_OK)  // a trace schedule: each env's trace
     return LBSIM_EDEVICE;
   if (h->plan.form == kStepWave) {
     ProfScope ps(h, s, 4);
@@ -1061,6 +1191,12 @@ int lbsim_set_trace(lbsim_t* h, const uint32_t* gap_us, const float* work, int64
   DeviceGuard g(h->device);
   const hipStream_t s = (hipStream_t)stream;
   if (hipStreamSynchronize(s) != hipSuccess) return fail(h, LBSIM_EDEVICE, "stream sync failed");
+  trace_sel_drop(h);  // a new trace: every env replays it (the bank of one trace)
+  h->bank_begin.clear();
+  if (h->bank_begin_dev) {
+    (void)hipFree(h->bank_begin_dev);
+    h->bank_begin_dev = nullptr;
+  }
   if (h->trace_buf) {
     (void)hipFree(h->trace_buf);
     h->trace_buf = nullptr;
@@ -1080,7 +1216,174 @@ int lbsim_set_trace(lbsim_t* h, const uint32_t* gap_us, const float* work, int64
   h->st.trace_gap = g_dev;
   h->st.trace_work = w_dev;
   h->prm.trace_rows = (uint32_t)rows;
+  h->bank_begin = {0, rows};
   return LBSIM_OK;
+}
+
+int lbsim_set_trace_bank(lbsim_t* h, const uint32_t* gap_us, const float* work,
+                         const int64_t* row_begin, int n_traces, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->prm.trace)
+    return fail(h, LBSIM_EINVAL, "lbsim_set_trace_bank needs arrival_source TRACE");
+  if (gap_us == nullptr || work == nullptr || row_begin == nullptr)
+    return fail(h, LBSIM_EINVAL, "trace bank: need device gap_us / work and host row_begin");
+  if (n_traces < 1 || n_traces > 4096)
+    return fail(h, LBSIM_EINVAL, "trace bank: n_traces must be in [1, 4096] (got %d)", n_traces);
+  if (row_begin[0] != 0) return fail(h, LBSIM_EINVAL, "trace bank: row_begin[0] must be 0");
+  for (int t = 0; t < n_traces; ++t)
+    if (row_begin[t + 1] <= row_begin[t])
+      return fail(h, LBSIM_EINVAL, "trace bank: trace %d has no rows (row_begin must ascend)", t);
+  const int64_t rows = row_begin[n_traces];
+  if (rows > (int64_t)0x7FFFFFFF)
+    return fail(h, LBSIM_EINVAL, "trace bank: %lld rows in all, need fewer than 2^31",
+                (long long)rows);
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(h, LBSIM_EDEVICE, "stream sync failed");
+  trace_sel_drop(h);  // a new bank: every env back on its trace 0
+  const size_t n = (size_t)rows;
+  // a bank of the size of the one it replaces is rewritten in place (a captured graph keeps
+  // valid pointers and offsets of the same count); any other moves the buffer
+  const bool same = h->trace_buf != nullptr && (int)h->bank_begin.size() == n_traces + 1 &&
+                    h->bank_begin.back() == rows;
+  if (!same) {
+    if (h->trace_buf) (void)hipFree(h->trace_buf);
+    if (h->bank_begin_dev) (void)hipFree(h->bank_begin_dev);
+    h->trace_buf = nullptr;
+    h->bank_begin_dev = nullptr;
+    h->bank_begin.clear();
+    h->prm.trace_rows = 0;
+    if (hipMalloc(&h->trace_buf, n * 8) != hipSuccess) {
+      h->trace_buf = nullptr;
+      return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", n * 8);
+    }
+  }
+  uint32_t* g_dev = (uint32_t*)h->trace_buf;
+  float* w_dev = (float*)(g_dev + n);
+  if (hipMemcpyAsync(g_dev, gap_us, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(w_dev, work, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "trace bank copy failed");
+  h->st.trace_gap = g_dev;
+  h->st.trace_work = w_dev;
+  h->prm.trace_rows = (uint32_t)row_begin[1];  // no selection: every env on trace 0
+  h->bank_begin.assign(row_begin, row_begin + n_traces + 1);
+  if (h->bank_begin_dev != nullptr) {  // rewritten in place: the offsets too
+    const int rc = bank_begin_upload(h);
+    if (rc != LBSIM_OK) return rc;
+  }
+  return LBSIM_OK;
+}
+
+int lbsim_set_trace_schedule(lbsim_t* h, const int32_t* trace_id, int rows, int P,
+                             int steps_per_phase, int wrap, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->prm.trace)
+    return fail(h, LBSIM_EINVAL, "a trace schedule needs arrival_source TRACE");
+  if (h->bank_begin.empty())
+    return fail(h, LBSIM_EINVAL, "trace schedule: call lbsim_set_trace_bank (or lbsim_set_trace) "
+                                 "first");
+  if (trace_id == nullptr) return fail(h, LBSIM_EINVAL, "trace schedule: trace_id is NULL");
+  if (h->prm.lf_thr != 0u)
+    return fail(h, LBSIM_ENOTSUP, "a trace selection on a lost-FIN handle (lost_fin_prob > 0): "
+                                  "the bucket-wait mean is derived from the handle's one arrival "
+                                  "rate (a bank with every env on trace 0 is allowed)");
+  if (P < 1 || P > 4096)
+    return fail(h, LBSIM_EINVAL, "trace schedule: phases must be in [1, 4096] (got %d)", P);
+  if (steps_per_phase < 1)
+    return fail(h, LBSIM_EINVAL, "trace schedule: steps_per_phase must be >= 1 (got %d)",
+                steps_per_phase);
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "trace schedule: rows must be 1 or num_envs = %d (got %d)", h->B,
+                rows);
+  const size_t N = (size_t)h->B * (size_t)P;
+  if (N > (size_t)INT32_MAX)
+    return fail(h, LBSIM_ENOMEM, "trace schedule: num_envs * phases = %zu exceeds 2^31 - 1 table "
+                                 "elements", N);
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  if (h->bank_begin_dev == nullptr) {
+    const int rc = bank_begin_upload(h);
+    if (rc != LBSIM_OK) return rc;
+  }
+  // the tables: allocated by the first call for this P, rewritten in place by later ones
+  void* buf = h->tsel_buf;
+  const bool fresh = buf == nullptr || h->tsel_alloc_P != P;
+  if (fresh && hipMalloc(&buf, trace_sel_bytes(h, P)) != hipSuccess)
+    return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", trace_sel_bytes(h, P));
+  auto give_up = [&](int code, const char* what) {
+    if (fresh) (void)hipFree(buf);  // (waits for the device)
+    return fail(h, code, "trace schedule: %s", what);
+  };
+  const TraceSelBuf t = trace_sel_at(h, buf, P);
+  const int T = (int)h->bank_begin.size() - 1;
+  if (hipMemsetAsync(t.bad, 0, sizeof(uint32_t), s) != hipSuccess)
+    return give_up(LBSIM_EDEVICE, "hipMemsetAsync failed");
+  hipLaunchKernelGGL(trace_table_kernel, dim3(blocks256(N)), dim3(256), 0, s, trace_id,
+                     (int64_t)(rows == 1 ? 0 : P), h->B, P, T, t.staging, t.bad);
+  if (launch_check(h, "trace_table_kernel") != LBSIM_OK) {
+    if (fresh) (void)hipFree(buf);
+    return LBSIM_EDEVICE;
+  }
+  uint32_t nbad = 0;
+  if (hipMemcpyAsync(&nbad, t.bad, sizeof(nbad), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return give_up(LBSIM_EDEVICE, "conversion failed");
+  if (nbad != 0u) {  // nothing live was touched: the previous selection stays in force
+    if (fresh) (void)hipFree(buf);
+    return fail(h, LBSIM_EINVAL, "trace schedule: %u id(s) outside [0, %d)", nbad, T);
+  }
+  if (hipMemcpyAsync(t.live, t.staging, N * sizeof(int32_t), hipMemcpyDeviceToDevice, s) !=
+      hipSuccess)
+    return give_up(LBSIM_EDEVICE, "device copy failed");
+  if (fresh) {
+    if (h->tsel_buf != nullptr) (void)hipFree(h->tsel_buf);  // (waits for the device)
+    h->tsel_buf = buf;
+    h->tsel_alloc_P = P;
+  }
+  h->tsel_P = P;
+  h->tsel_H = steps_per_phase;
+  h->tsel_wrap = wrap != 0 ? 1 : 0;
+  // every env's descriptor is valid from here on: a masked reset rewrites only its own envs'
+  const int rc = trace_select(h, nullptr, kModeStep, s);
+  if (rc != LBSIM_OK) {
+    trace_sel_drop(h);
+    return rc;
+  }
+  set_env_trace(h->st, t.cur);
+  return LBSIM_OK;
+}
+
+int lbsim_clear_trace_schedule(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->prm.trace)
+    return fail(h, LBSIM_EINVAL, "a trace schedule needs arrival_source TRACE");
+  const int P = h->tsel_alloc_P;
+  trace_sel_drop(h);
+  if (h->tsel_buf == nullptr) return LBSIM_OK;
+  // a step captured into a graph while the selection was set keeps gathering from the tables:
+  // they take id 0 in every phase (no stream argument: the whole device is waited for)
+  DeviceGuard g(h->device);
+  const TraceSelBuf t = trace_sel_at(h, h->tsel_buf, P);
+  if (hipDeviceSynchronize() != hipSuccess ||
+      hipMemset(t.live, 0, (size_t)h->B * (size_t)P * sizeof(int32_t)) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "trace schedule: clearing the tables failed");
+  return LBSIM_OK;
+}
+
+int lbsim_env_trace(lbsim_t* h, int32_t* trace_id_out, int32_t* phase_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (trace_id_out == nullptr && phase_out == nullptr) return LBSIM_OK;
+  DeviceGuard g(h->device);
+  const SimParams& p = h->prm;
+  const int32_t* ids =
+      h->tsel_P > 0 ? trace_sel_at(h, h->tsel_buf, h->tsel_P).live : (const int32_t*)nullptr;
+  hipLaunchKernelGGL(trace_gather_kernel, dim3(blocks256((size_t)h->B)), dim3(256), 0,
+                     (hipStream_t)stream, h->st.ep_step, (const uint8_t*)nullptr, 0, h->B,
+                     h->tsel_P, h->tsel_H, h->tsel_wrap, p.max_steps, p.next_reset, ids,
+                     (const uint32_t*)nullptr, (uint2*)nullptr, trace_id_out, phase_out);
+  return launch_check(h, "trace_gather_kernel");
 }
 
 int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* server_rate,
@@ -1125,8 +1428,7 @@ int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* serv
     ok &= hipMemcpyAsync(live.scale, stg.scale, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
   }
   if (!ok) return fail(h, LBSIM_EDEVICE, "per-env rates: device copy failed");
-  h->st.env_gap = live.gap;
-  h->st.env_scale = live.scale;
+  set_env_arrays(h, live.gap, live.scale);
   h->rates_on = true;
   return LBSIM_OK;
 }
@@ -1135,8 +1437,7 @@ int lbsim_clear_env_rates(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
   sched_drop(h);
   h->rates_on = false;
-  h->st.env_gap = nullptr;
-  h->st.env_scale = nullptr;
+  set_env_arrays(h, nullptr, nullptr);
   if (h->rates_buf == nullptr) return LBSIM_OK;
   // a step captured into a graph while the rates were set keeps reading the live arrays: they
   // take the config's rates (no stream argument here, so the whole device is waited for)
@@ -1253,8 +1554,7 @@ int lbsim_set_rate_schedule(lbsim_t* h, const float* arrival_rate, const float* 
   }
   // the dynamics kernels read the per-env arrays that sched_select fills before every launch
   float* const cur = sched_cur(h, buf, P);
-  h->st.env_gap = cur;
-  h->st.env_scale = cur + B;
+  set_env_arrays(h, cur, cur + B);
   h->sched_P = P;
   h->sched_H = steps_per_phase;
   h->sched_wrap = wrap != 0 ? 1 : 0;

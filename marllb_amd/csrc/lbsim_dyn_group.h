@@ -293,7 +293,8 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
                                                  LaneState<1>& E, SrvLane& V, int s, int gbase,
                                                  int n_alias, const GroupConst& gc, int2* win,
                                                  int32_t* atab, int4* acache, uint2* const my_res,
-                                                 int2* const my_ring, bool fs_on = false) {
+                                                 int2* const my_ring, bool fs_on = false,
+                                                 const TraceSel& ts = TraceSel{}) {
   constexpr int WL = kGroupWL;
   constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
   constexpr bool alias = POLICY == kPolicyAlias;
@@ -316,7 +317,7 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
   // TRACE: the trace row of arrival kbase, advanced by the arrivals consumed between refills (one
   // 64-bit modulo per step instead of one per drawn arrival)
   uint32_t kbase = E.arr_idx + 1u, rbase = 0u;
-  if constexpr (TRACE) rbase = trace_row(p, E.gid, E.episode, kbase);
+  if constexpr (TRACE) rbase = trace_row_in(ts.rows, E.gid, E.episode, kbase);
   for (;;) {
     if ((it & (uint32_t)(G - 1)) == 0u) {
       cbase = E.arr_idx + 1u;
@@ -332,14 +333,14 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
       int32_t gap;
       float wk;
       if constexpr (TRACE) {
-        const uint32_t rows = p.trace_rows;
+        const uint32_t rows = ts.rows;  // the env's own trace: rows [base, base + rows)
         rbase += cbase - kbase;  // <= G arrivals since the last refill
         kbase = cbase;
         while (rbase >= rows) rbase -= rows;
         uint32_t r = rbase + (uint32_t)s;
         while (r >= rows) r -= rows;
-        gap = (int32_t)st.trace_gap[r];
-        wk = st.trace_work[r];
+        gap = (int32_t)st.trace_gap[ts.base + r];
+        wk = st.trace_work[ts.base + r];
       } else {  // (the two logs as one packed-f32 polynomial measured 2 % slower: r05t)
         gap = (int32_t)(-lb_logf(u01_open0(d.x)) * gc.mean_gap);
         wk = -lb_logf(u01_open0(d.y));
@@ -508,7 +509,8 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                                                LaneState<1>& E, SrvLane& V, uint32_t b, int s,
                                                int gbase, float w_own, const float (&wall)[G],
                                                int2* win, int32_t* atab, int4* acache,
-                                               bool fs_on = false) {
+                                               bool fs_on = false,
+                                               const TraceSel& ts = TraceSel{}) {
   constexpr int WL = kGroupWL;
   const int S = p.S, Q = p.Q;
   const int32_t dt = p.dt_us;
@@ -632,15 +634,15 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
     group_event_loop<G, POLICY, TRACE, false, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                                    acache, my_res, my_ring, fs_on);
+                                                    acache, my_res, my_ring, fs_on, ts);
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
   } else if (__all(finite)) {
     group_event_loop<G, POLICY, TRACE, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                             acache, my_res, my_ring);
+                                             acache, my_res, my_ring, false, ts);
   } else {
     group_event_loop<G, POLICY, TRACE, false>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                              acache, my_res, my_ring);
+                                              acache, my_res, my_ring, false, ts);
   }
 
   // ---- rebase to the next step's start (this lane's server)
@@ -707,6 +709,8 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
 
   LaneState<1> E;
   E.gid = p.env_id_offset + b;
+  TraceSel ts{};  // TRACE: the env's trace (a bank selection, else the handle's first trace)
+  if constexpr (TRACE) ts = env_trace_sel(st, p, b);
   SrvLane V;
   V.act = s < S;
   V.over = 0u;
@@ -741,7 +745,7 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     E.clock = 0u;
     E.dropped = 0u;
     E.arr_idx = 0u;
-    draw_arrival<1>(st, p, E, b, 0);
+    draw_arrival<1, TRACE>(st, p, E, b, 0, ts);
     V.cnt = 0;
     V.head_tc = 0;
     V.head = 0;
@@ -861,12 +865,12 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
   if constexpr (MODE == kModeStep) {
     load_in();
     sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w_own, wall, win, atab,
-                                           acache, fs_on);
+                                           acache, fs_on, ts);
   } else if constexpr (MODE == kModeReset) {
     reset_in();
     for (int k = 0; k < p.warmup_steps; ++k)
       sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, 1.0f, wall, win, atab,
-                                             acache, fs_on);
+                                             acache, fs_on, ts);
     reset_out(0);
   } else {
     // kModeStepNR (next-step auto-reset): an env whose last step returned done resets in place of
@@ -882,7 +886,7 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     const float w = rs ? 1.0f : w_own;
     for (int k = 0; k < nsteps; ++k)
       sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w, wall, win, atab,
-                                             acache, fs_on);
+                                             acache, fs_on, ts);
     if (rs) reset_out(-1);
   }
 

@@ -72,6 +72,7 @@ struct WaveEnv {
   float next_work;
   uint32_t u2, u3;
   float mean_gap;  // the env's mean arrival gap in us (env_mean_gap), read once at kernel entry
+  uint32_t tbase, trows;  // TRACE: the env's trace (env_trace_sel), read once at kernel entry
 };
 
 // One batch of drawn arrivals (lane j: arrival base + j) and the log of the processed ones.
@@ -122,7 +123,7 @@ __device__ __forceinline__ void wave_draw_batch(const DevState& st, const SimPar
   int32_t gap;
   float wk;
   if constexpr (TRACE) {
-    const uint32_t r = trace_row(p, E.gid, E.episode, k);
+    const uint32_t r = E.tbase + trace_row_in(E.trows, E.gid, E.episode, k);
     gap = (int32_t)st.trace_gap[r];
     wk = st.trace_work[r];
   } else {
@@ -538,6 +539,11 @@ __device__ __forceinline__ bool dyn_wave_env(const DevState& st, const SimParams
   WaveEnv E;
   E.gid = p.env_id_offset + b;
   E.mean_gap = env_mean_gap(st, p, b);
+  if constexpr (TRACE) {  // the env's trace (a bank selection, else the handle's first trace)
+    const TraceSel ts = env_trace_sel(st, p, b);
+    E.tbase = ts.base;
+    E.trows = ts.rows;
+  }
   WaveSrv V;
   V.act = lane < S;
   V.scale = p.svc_scale[0];
@@ -574,7 +580,7 @@ __device__ __forceinline__ bool dyn_wave_env(const DevState& st, const SimParams
       int32_t gap;
       float wk;
       if constexpr (TRACE) {
-        const uint32_t r = trace_row(p, E.gid, E.episode, 0u);
+        const uint32_t r = E.tbase + trace_row_in(E.trows, E.gid, E.episode, 0u);
         gap = (int32_t)st.trace_gap[r];
         wk = st.trace_work[r];
       } else {

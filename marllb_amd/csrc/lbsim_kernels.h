@@ -91,16 +91,30 @@ struct DevState {
   // running normalisation [B*S*11] (nullptr when disabled)
   double* norm_mean;
   double* norm_std;
-  // arrival trace (TRACE source; nullptr otherwise), shared by all envs: us gap before each row,
-  // mean-1 work of each row
+  // arrival trace (TRACE source; nullptr otherwise): us gap before each row, mean-1 work of each
+  // row.  A bank (lbsim_set_trace_bank) holds its traces back to back in these two arrays.
   const uint32_t* trace_gap;
   const float* trace_work;
   // per-env workload (lbsim_set_env_rates; nullptr = the shared SimParams::mean_gap_us /
   // svc_scale[]): env_gap[b] = the env's mean arrival gap in us, env_scale[b*S + s] = 1e6 / mu of
   // its server s.  Read once in each dynamics kernel's prologue; not part of the snapshot.
+  // A TRACE handle draws no gap, so there env_gap carries the trace selection instead (DESIGN.md
+  // §3.14: the struct keeps its layout and every kernel its argument segment): read through
+  // env_trace(st), [B] {first bank row, rows} of the trace each env replays
+  // (lbsim_set_trace_schedule; nullptr = rows [0, SimParams::trace_rows) for every env), written
+  // by trace_gather_kernel before each launch and read by the TRACE instantiations alone, once,
+  // in their prologue.
   const float* env_gap;
   const float* env_scale;
 };
+// A TRACE handle's trace selection (DevState::env_gap's word, which such a handle never reads as
+// a gap): the pointer is converted, never the values behind it.
+__host__ __device__ inline const uint2* env_trace(const DevState& st) {
+  return reinterpret_cast<const uint2*>(st.env_gap);
+}
+inline void set_env_trace(DevState& st, const uint2* desc) {
+  st.env_gap = reinterpret_cast<const float*>(desc);
+}
 
 // Exact flow statistics (lbsim_flow_stats_enable; nullptr = off), cumulative over
 // the steps since they were last cleared, per server [B*S]: completed flows, the sum and the
@@ -336,6 +350,31 @@ __device__ __forceinline__ uint32_t trace_row(const SimParams& p, uint32_t gid, 
   return (uint32_t)(v % (uint64_t)p.trace_rows);
 }
 
+// The trace an env replays: rows [base, base + rows) of DevState::trace_gap / trace_work.
+struct TraceSel {
+  uint32_t base, rows;
+};
+// Env b's trace: its descriptor (a handle with a trace selection; a wave-uniform null test, made
+// once in the prologue of a TRACE instantiation) or the handle's first trace.
+__device__ __forceinline__ TraceSel env_trace_sel(const DevState& st, const SimParams& p,
+                                                  uint32_t b) {
+  TraceSel t{0u, p.trace_rows};
+  if (const uint2* const sel = env_trace(st)) {
+    const uint2 d = sel[b];
+    t.base = d.x;
+    t.rows = d.y;
+  }
+  return t;
+}
+// The row rule inside a trace of `rows` rows (trace_row with the env's own divisor): a 64-bit
+// modulo, so only in a prologue or at a refill, never once per arrival.
+__device__ __forceinline__ uint32_t trace_row_in(uint32_t rows, uint32_t gid, uint32_t episode,
+                                                 uint32_t k) {
+  const uint64_t v = (uint64_t)gid * kTraceEnvStride +
+                     (uint64_t)(episode - 1u) * kTraceEpisodeStride + (uint64_t)k;
+  return (uint32_t)(v % (uint64_t)rows);
+}
+
 // ================================================================ dynamics (one lane = one env)
 
 // Queue window in LDS: the first WL entries of each server's FIFO live in LDS, laid out
@@ -381,8 +420,8 @@ struct LaneState {
   uint32_t gid;
   uint32_t downm;         // bit s: server s is down (fail_prob > 0), not eligible as a full one
   uint32_t bigm;          // bit s: server s's kHcBig flag
-  // TRACE: row of arrival arr_idx + 1 and its prefetched gap / work (loaded an arrival ahead so
-  // the event loop never waits on the trace)
+  // TRACE: row of arrival arr_idx + 1 inside the env's trace (TraceSel) and its prefetched gap /
+  // work (loaded an arrival ahead so the event loop never waits on the trace)
   uint32_t row;
   int32_t pf_gap;
   float pf_work;
@@ -536,12 +575,20 @@ __device__ __forceinline__ void arrival_from_draw(float mean_gap_us, const u32x4
   u3 = d.w;
 }
 
-template <int MAXS>
+// TRACE (the caller's instantiation): the row of the env's own trace ts.
+template <int MAXS, bool TRACE = false>
 __device__ __forceinline__ void draw_arrival(const DevState& st, const SimParams& p,
-                                             LaneState<MAXS>& L, uint32_t b, int32_t t_prev) {
+                                             LaneState<MAXS>& L, uint32_t b, int32_t t_prev,
+                                             const TraceSel& ts = TraceSel{}) {
   const u32x4 d = philox4x32_10(u32x4{L.arr_idx, L.gid, L.episode, kStreamArrival << 24},
                                 p.key0, p.key1);
-  if (p.trace) {
+  if constexpr (TRACE) {
+    const uint32_t r = ts.base + trace_row_in(ts.rows, L.gid, L.episode, L.arr_idx);
+    L.next_arr = t_prev + (int32_t)st.trace_gap[r];
+    L.next_work = st.trace_work[r];
+    L.u2 = d.z;
+    L.u3 = d.w;
+  } else if (p.trace) {
     const uint32_t r = trace_row(p, L.gid, L.episode, L.arr_idx);
     L.next_arr = t_prev + (int32_t)st.trace_gap[r];
     L.next_work = st.trace_work[r];
@@ -553,10 +600,15 @@ __device__ __forceinline__ void draw_arrival(const DevState& st, const SimParams
 }
 
 // TRACE: position the prefetch at arrival arr_idx + 1 (kernel entry).
-template <int MAXS>
+template <int MAXS, bool TRACE = false>
 __device__ __forceinline__ void trace_prefetch(const DevState& st, const SimParams& p,
-                                               LaneState<MAXS>& L) {
-  if (p.trace) {
+                                               LaneState<MAXS>& L,
+                                               const TraceSel& ts = TraceSel{}) {
+  if constexpr (TRACE) {
+    L.row = trace_row_in(ts.rows, L.gid, L.episode, L.arr_idx + 1u);
+    L.pf_gap = (int32_t)st.trace_gap[ts.base + L.row];
+    L.pf_work = st.trace_work[ts.base + L.row];
+  } else if (p.trace) {
     L.row = trace_row(p, L.gid, L.episode, L.arr_idx + 1u);
     L.pf_gap = (int32_t)st.trace_gap[L.row];
     L.pf_work = st.trace_work[L.row];
@@ -753,7 +805,8 @@ __device__ __forceinline__ void event_loop(const DevState& st, const SimParams& 
                                            LaneState<MAXS>& L, const Lds& l,
                                            const EvConst<MAXS>& ec, const double (&den)[MAXS],
                                            const double (&rcp)[MAXS], int n_alias,
-                                           uint2* const my_res, int2* const my_ring) {
+                                           uint2* const my_res, int2* const my_ring,
+                                           const TraceSel& ts = TraceSel{}) {
   constexpr int WL = LaneState<MAXS>::WL;
   constexpr bool REGF = MAXS <= 8;
   constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
@@ -995,9 +1048,9 @@ __device__ __forceinline__ void event_loop(const DevState& st, const SimParams& 
       nu2 = d.z;
       nu3 = d.w;
       if (arr) {
-        L.row = (L.row + 1u == p.trace_rows) ? 0u : L.row + 1u;
-        L.pf_gap = (int32_t)st.trace_gap[L.row];
-        L.pf_work = st.trace_work[L.row];
+        L.row = (L.row + 1u == ts.rows) ? 0u : L.row + 1u;
+        L.pf_gap = (int32_t)st.trace_gap[ts.base + L.row];
+        L.pf_work = st.trace_work[ts.base + L.row];
       }
     } else {
       na = ta + (int32_t)(-lb_logf(u01_open0(d.x)) * ec.mean_gap);
@@ -1056,7 +1109,7 @@ __device__ __forceinline__ void event_loop(const DevState& st, const SimParams& 
 template <int MAXS, int POLICY, bool TRACE>
 __device__ __forceinline__ void sim_step(const DevState& st, const SimParams& p,
                                          LaneState<MAXS>& L, uint32_t b, const float (&w)[MAXS],
-                                         const Lds& l) {
+                                         const Lds& l, const TraceSel& ts = TraceSel{}) {
   constexpr int WL = LaneState<MAXS>::WL;
   const int S = p.S, Q = p.Q;
   const int32_t dt = p.dt_us;
@@ -1170,9 +1223,9 @@ __device__ __forceinline__ void sim_step(const DevState& st, const SimParams& p,
   //      have finite scores runs the loop without the NaN fallbacks (a wave-uniform choice).
   const EvConst<MAXS> ec = ev_const<MAXS>(st, p, b, base_ms, base_rem);
   if ((lsq || alias || __all(finite_scores)) && !p.leak && st.res_dur == nullptr)
-    event_loop<MAXS, POLICY, TRACE, true>(st, p, L, l, ec, den, rcp, n_alias, my_res, my_ring);
+    event_loop<MAXS, POLICY, TRACE, true>(st, p, L, l, ec, den, rcp, n_alias, my_res, my_ring, ts);
   else
-    event_loop<MAXS, POLICY, TRACE, false>(st, p, L, l, ec, den, rcp, n_alias, my_res, my_ring);
+    event_loop<MAXS, POLICY, TRACE, false>(st, p, L, l, ec, den, rcp, n_alias, my_res, my_ring, ts);
 
   // ---- rebase relative times to the next step's start: the LDS window in place, the HBM ring
   //      entries beyond it read-modify-written (queues longer than WL only)
@@ -1309,14 +1362,16 @@ __global__ void __launch_bounds__(64 * kDynWaves<MAXS>)
   L.gid = p.env_id_offset + b;
 
   if (mode == kModeReset && reset_mask != nullptr && reset_mask[b] == 0) return;
+  TraceSel ts{};  // TRACE: the env's trace (a bank selection, else the handle's first trace)
+  if constexpr (TRACE) ts = env_trace_sel(st, p, b);
   float w[MAXS];
   auto reset_in = [&]() {  // a new episode (env.py:186-213): its first arrival, empty servers
     L.episode = st.episode[b] + 1u;
     L.clock = 0u;
     L.dropped = 0u;
     L.arr_idx = 0u;
-    draw_arrival<MAXS>(st, p, L, b, 0);
-    trace_prefetch<MAXS>(st, p, L);
+    draw_arrival<MAXS, TRACE>(st, p, L, b, 0, ts);
+    trace_prefetch<MAXS, TRACE>(st, p, L, ts);
     clear_servers<MAXS>(p, L, l);
     if (p.leak)  // a new episode: no lost flows yet (n_flow_on_mode VPP)
       for (int s = 0; s < S; ++s) st.lost_on[b * (uint32_t)S + (uint32_t)s] = 0u;
@@ -1332,7 +1387,7 @@ __global__ void __launch_bounds__(64 * kDynWaves<MAXS>)
     L.next_work = st.next_work[b];
     L.u2 = st.next_u2[b];
     L.u3 = st.next_u3[b];
-    trace_prefetch<MAXS>(st, p, L);
+    trace_prefetch<MAXS, TRACE>(st, p, L, ts);
     load_servers<MAXS>(st, p, L, b, l);
 #pragma unroll
     for (int s = 0; s < MAXS; ++s)
@@ -1346,19 +1401,19 @@ __global__ void __launch_bounds__(64 * kDynWaves<MAXS>)
   };
   if constexpr (mode == kModeStep) {
     load_in();
-    sim_step<MAXS, POLICY, TRACE>(st, p, L, b, w, l);
+    sim_step<MAXS, POLICY, TRACE>(st, p, L, b, w, l, ts);
   } else if constexpr (mode == kModeReset) {
     reset_in();
-    for (int k = 0; k < p.warmup_steps; ++k) sim_step<MAXS, POLICY, TRACE>(st, p, L, b, w, l);
+    for (int k = 0; k < p.warmup_steps; ++k) sim_step<MAXS, POLICY, TRACE>(st, p, L, b, w, l, ts);
     reset_out(0);
   } else {  // kModeStepNR: an env done last step resets in place of stepping (ep_step = -1)
     if (st.ep_step[b] >= p.max_steps) {
       reset_in();
-      for (int k = 0; k < p.warmup_steps; ++k) sim_step<MAXS, POLICY, TRACE>(st, p, L, b, w, l);
+      for (int k = 0; k < p.warmup_steps; ++k) sim_step<MAXS, POLICY, TRACE>(st, p, L, b, w, l, ts);
       reset_out(-1);
     } else {
       load_in();
-      sim_step<MAXS, POLICY, TRACE>(st, p, L, b, w, l);
+      sim_step<MAXS, POLICY, TRACE>(st, p, L, b, w, l, ts);
     }
   }
   store_servers<MAXS>(st, p, L, b, l, mode == kModeReset ? nullptr : assign_out);

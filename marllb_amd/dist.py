@@ -5,7 +5,8 @@ rank r owns global ids [r*B, (r+1)*B) through `env_id_offset` and ranks never ex
 only collectives are around measurement: a barrier before/after the timed region and max/sum
 reductions of the per-rank results.  Weak scaling: per-rank B is fixed as world grows.
 Per-env rates (VecLoadBalanceEnv.set_rates) shard the same way: a rank passes its own rows,
-arrays[lo:hi] of the global (B,) / (B, S) arrays.
+arrays[lo:hi] of the global (B,) / (B, S) arrays; so do rate schedules and trace ids
+(set_rate_schedule, set_env_trace, set_trace_schedule): Shard.rows(x) is a rank's slice.
 """
 import os
 from dataclasses import dataclass
@@ -27,6 +28,14 @@ class Shard:
 
     def global_ids(self):
         return range(self.env_id_offset, self.env_id_offset + self.envs_per_rank)
+
+    def rows(self, x):
+        """This rank's rows x[lo:hi] of a per-env array of the whole batch (rates, a rate
+        schedule, trace ids: their first dimension is the global env id)."""
+        if len(x) != self.global_envs:
+            raise ValueError(f"expected {self.global_envs} rows, one per env of the whole batch "
+                             f"(got {len(x)})")
+        return x[self.env_id_offset:self.env_id_offset + self.envs_per_rank]
 
 
 def from_env(envs_per_rank: int) -> Shard:

@@ -97,6 +97,15 @@ def _device_index(device) -> int:
     return torch.cuda.current_device() if d.index is None else d.index
 
 
+def _is_bank(trace) -> bool:
+    """trace= given as a bank: a list / tuple of traces or a marllb_amd.trace.TraceBank."""
+    return isinstance(trace, (list, tuple)) or hasattr(trace, "row_begin")
+
+
+def _first_trace(trace):
+    return trace[0] if _is_bank(trace) else trace
+
+
 def make_config(num_envs: int, num_servers: int = 4, action_type: str = "discrete",
                 discrete_weights: Optional[List[float]] = None, max_weight: float = 10.0,
                 min_weight: float = 0.1, reward_metric: str = "jain",
@@ -116,7 +125,9 @@ def make_config(num_envs: int, num_servers: int = 4, action_type: str = "discret
 
     server_rates defaults to identical servers at utilisation `load`: mu = rate / (load * S).
     trace (marllb_amd.trace.Trace): replay its arrivals (LBSIM_ARRIVAL_TRACE); its empirical rate
-    replaces arrival_rate.  The arrays themselves go to the handle (Handle.set_trace).
+    replaces arrival_rate.  The arrays themselves go to the handle (Handle.set_trace).  A list of
+    traces or a marllb_amd.trace.TraceBank: a bank (Handle.set_trace_bank); its first trace's rate
+    fills arrival_rate.
     dyn_mapping: "auto" | "env" (one lane per env) | "server" (one lane per server): how the
     dynamics kernel lays envs onto lanes; results are identical, only speed differs.
     step_kernel: "auto" | "split" (dynamics launch + observe launch) | "fused" (one launch that
@@ -172,7 +183,7 @@ def make_config(num_envs: int, num_servers: int = 4, action_type: str = "discret
     cfg.assign_policy = _lib.POLICIES.index(assign_policy)
     if trace is not None:
         cfg.arrival_source = _lib.ARRIVAL_TRACE
-        arrival_rate = float(trace.rate)
+        arrival_rate = float(_first_trace(trace).rate)
     cfg.arrival_rate = float(arrival_rate)
     if server_rates is None:
         server_rates = [float(arrival_rate) / (float(load) * num_servers)] * num_servers
@@ -281,6 +292,45 @@ class Handle:
     def _stream(self) -> int:
         torch = _torch()
         return torch.cuda.current_stream(torch.device("cuda", self.device_index)).cuda_stream
+
+    def set_trace_bank(self, bank) -> None:
+        """Copy a marllb_amd.trace.TraceBank (or a list of traces) to the device and install it
+        (lbsim_set_trace_bank); every env is on trace 0 afterwards."""
+        from .trace import TraceBank
+        torch = _torch()
+        bank = bank if isinstance(bank, TraceBank) else TraceBank(bank)
+        dev = torch.device("cuda", self.device_index)
+        gap = torch.from_numpy(bank.gap_us.view(np.int32)).to(dev)
+        work = torch.from_numpy(bank.work).to(dev)
+        begin = np.ascontiguousarray(bank.row_begin, np.int64)
+        self.check(self.lib.lbsim_set_trace_bank(
+            self.h, ctypes.c_void_p(gap.data_ptr()), ctypes.c_void_p(work.data_ptr()),
+            begin.ctypes.data_as(ctypes.c_void_p), len(bank), ctypes.c_void_p(self._stream())))
+
+    def set_trace_schedule(self, trace_id, *, rows: int, phases: int, steps_per_phase: int = 1,
+                           wrap: bool = True) -> None:
+        """A trace schedule (lbsim_set_trace_schedule): trace_id (rows, P) int32 contiguous tensor
+        on the handle's device, rows = 1 or B."""
+        self.check(self.lib.lbsim_set_trace_schedule(
+            self.h, ctypes.c_void_p(trace_id.data_ptr()), int(rows), int(phases),
+            int(steps_per_phase), 1 if wrap else 0, ctypes.c_void_p(self._stream())))
+
+    def clear_trace_schedule(self) -> None:
+        """Every env back to trace 0 (lbsim_clear_trace_schedule)."""
+        self.check(self.lib.lbsim_clear_trace_schedule(self.h))
+
+    def env_trace(self):
+        """(trace_id (B,), phase (B,)) int32 device tensors: the trace and the trace-schedule
+        phase each env's next step launch will use (lbsim_env_trace)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        B = int(self.cfg.num_envs)
+        ids = torch.empty(B, dtype=torch.int32, device=dev)
+        phase = torch.empty(B, dtype=torch.int32, device=dev)
+        self.check(self.lib.lbsim_env_trace(self.h, ctypes.c_void_p(ids.data_ptr()),
+                                            ctypes.c_void_p(phase.data_ptr()),
+                                            ctypes.c_void_p(self._stream())))
+        return ids, phase
 
     def set_env_rates(self, arrival=None, server=None) -> None:
         """Per-env workload (lbsim_set_env_rates): arrival (B,) and / or server (B, S) f32
@@ -471,7 +521,10 @@ class VecLoadBalanceEnv:
         if flow_stats:
             self.handle.enable_flow_stats()
         if self.trace is not None:
-            self.handle.set_trace(self.trace)
+            if _is_bank(self.trace):
+                self.handle.set_trace_bank(self.trace)
+            else:
+                self.handle.set_trace(self.trace)
         self._reset_done = False
         # upper bound on every env's episode step since the last full reset: while it is below
         # max_steps no env can be done, so the masked auto-reset launch is provably a no-op
@@ -770,6 +823,72 @@ class VecLoadBalanceEnv:
         """(B,) int32 device tensor: the schedule phase each env's next step will use (zeros
         without a schedule)."""
         return self.handle.rate_phase()
+
+    def set_trace_bank(self, bank) -> None:
+        """A bank of traces for a trace= env (a marllb_amd.trace.TraceBank or a list of traces):
+        one handle holds T traces and each env replays the one its id names (set_env_trace,
+        set_trace_schedule); every env is on trace 0 afterwards, and any selection is dropped.
+        Takes effect like set_trace: at the next reset for the arrivals not yet drawn."""
+        self.handle.set_trace_bank(bank)
+        self.trace = bank
+
+    def _trace_ids_arg(self, ids, name):
+        """Trace ids as a contiguous int32 tensor (rows, P) on the env's device: ids is (P,) for
+        one shared schedule or (B, P)."""
+        torch = _torch()
+        t = torch.as_tensor(ids)
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError(f"{name}: trace ids are integers (got {t.dtype})")
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if t.dim() != 2 or t.shape[1] < 1 or t.shape[0] not in (1, self.num_envs):
+            raise ValueError(f"{name}: expected (P,) or ({self.num_envs}, P), got "
+                             f"{tuple(torch.as_tensor(ids).shape)}")
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def set_env_trace(self, ids) -> None:
+        """Per-env trace selection for domain-randomised trace batches: ids (B,) in [0, T), a
+        tensor or array on any device; env b replays bank trace ids[b] from the next launch on
+        (the arrival already drawn keeps its time and work).  The one-phase case of
+        set_trace_schedule.  A shard passes its own rows, ids[lo:hi]
+        (marllb_amd.randomize.sample_trace_ids draws such ids)."""
+        torch = _torch()
+        t = torch.as_tensor(ids)
+        if t.dim() != 1 or t.shape[0] != self.num_envs:
+            raise ValueError(f"set_env_trace: expected ({self.num_envs},), got {tuple(t.shape)}")
+        self.set_trace_schedule(t.unsqueeze(1), steps_per_phase=1)
+
+    def set_trace_schedule(self, ids, steps_per_phase: int = 1, wrap: bool = True) -> None:
+        """A trace schedule for non-stationary trace workloads: P phases, each held for
+        steps_per_phase agent steps, cyclic (wrap) or clamped at the last phase; ids is (P,) for
+        one schedule shared by every env or (B, P), integers in [0, T), a numpy array or a tensor
+        on either device.  The phase rule and the reset rule are set_rate_schedule's
+        (marllb_amd.randomize.schedule_phase; a reset, warm-up and auto-reset included, runs at
+        phase 0).  A change of trace keeps the arrival already drawn; every later arrival reads
+        the new trace.  An id outside the bank: ValueError, the selection in force stays.  Not
+        supported with lost_fin_prob > 0 (LbsimError, code ENOTSUP).  Independent of a server-rate
+        schedule, which may be in force beside it.  Not part of get_state() (the episode step
+        is).  graph_mode: later calls with the same P rewrite the ids in place and replays see
+        them; a new P, steps_per_phase or wrap needs a new capture
+        (marllb_amd.randomize.diurnal_trace_schedule draws such tables)."""
+        t = self._trace_ids_arg(ids, "set_trace_schedule")
+        self.handle.set_trace_schedule(t, rows=int(t.shape[0]), phases=int(t.shape[1]),
+                                       steps_per_phase=steps_per_phase, wrap=wrap)
+
+    def clear_trace_schedule(self) -> None:
+        """Drop the trace selection: every env back to trace 0."""
+        self.handle.clear_trace_schedule()
+
+    @property
+    def env_trace(self):
+        """(B,) int32 device tensor: the bank trace each env's next step will replay (zeros
+        without a selection)."""
+        return self.handle.env_trace()[0]
+
+    @property
+    def trace_phase(self):
+        """(B,) int32 device tensor: the trace-schedule phase each env's next step will use."""
+        return self.handle.env_trace()[1]
 
     def flow_stats(self, per_server: bool = False, hist: bool = False) -> Dict[str, Any]:
         """The exact flow statistics since the last clear, as device tensors of shape (B,) or,

@@ -248,6 +248,29 @@ class VecMultiAgentLoadBalanceEnv:
     def rate_phase(self):
         return self.vec.rate_phase
 
+    def set_trace_bank(self, bank) -> None:
+        """A bank of traces: VecLoadBalanceEnv.set_trace_bank."""
+        self.vec.set_trace_bank(bank)
+
+    def set_env_trace(self, ids) -> None:
+        """Per-env trace ids (B,): VecLoadBalanceEnv.set_env_trace."""
+        self.vec.set_env_trace(ids)
+
+    def set_trace_schedule(self, ids, steps_per_phase: int = 1, wrap: bool = True) -> None:
+        """A trace schedule, (P,) shared or (B, P): VecLoadBalanceEnv.set_trace_schedule."""
+        self.vec.set_trace_schedule(ids, steps_per_phase, wrap)
+
+    def clear_trace_schedule(self) -> None:
+        self.vec.clear_trace_schedule()
+
+    @property
+    def env_trace(self):
+        return self.vec.env_trace
+
+    @property
+    def trace_phase(self):
+        return self.vec.trace_phase
+
     def flow_stats(self, per_server: bool = False, hist: bool = False):
         """Exact flow statistics of an env made with flow_stats=True: VecLoadBalanceEnv.flow_stats."""
         return self.vec.flow_stats(per_server, hist)

@@ -4,6 +4,8 @@ sample_rates draws one arrival rate and one set of server rates per env, so one 
 policy across light, heavy and overloaded clusters with fast, slow and heterogeneous servers.
 diurnal_schedule and burst_schedule draw per-env arrival schedules whose load moves inside an
 episode (VecLoadBalanceEnv.set_rate_schedule); schedule_phase states the phase rule.
+sample_trace_ids and diurnal_trace_schedule are their counterparts for a TRACE handle's bank of
+traces (VecLoadBalanceEnv.set_env_trace / set_trace_schedule).
 Pure torch; deterministic for a seeded generator.
 """
 from __future__ import annotations
@@ -125,3 +127,45 @@ def burst_schedule(arrival, phases: int, *, factor: float = 4.0, p_on: float = 0
         on[:, j] = torch.where(prev, u[:, j] >= float(p_off), u[:, j] < float(p_on))
     sched = a[:, None] * torch.where(on, float(factor), 1.0)
     return sched.clamp(*ARRIVAL_RANGE).to(device=device, dtype=torch.float32)
+
+
+# ---- trace banks (VecLoadBalanceEnv.set_env_trace / set_trace_schedule): the TRACE counterpart
+
+def sample_trace_ids(num_envs: int, num_traces: int, seed: int = 0, *, device=None):
+    """-> (B,) int32 trace ids, uniform over the bank's T traces: domain randomisation over the
+    load of a TRACE handle (VecLoadBalanceEnv.set_env_trace).  Deterministic for a seed."""
+    import torch
+
+    B, T = int(num_envs), int(num_traces)
+    if B < 1 or T < 1:
+        raise ValueError(f"need num_envs >= 1 and num_traces >= 1 (got {num_envs}, {num_traces})")
+    g = torch.Generator().manual_seed(int(seed))
+    return torch.randint(0, T, (B,), generator=g, dtype=torch.int64).to(device=device,
+                                                                        dtype=torch.int32)
+
+
+def diurnal_trace_schedule(bank_rates, phases: int, num_envs: int, *, amplitude=(0.2, 0.8),
+                           phase=(0.0, 1.0), seed: int = 0, device=None):
+    """-> (B, phases) int32 trace ids: diurnal_schedule over a bank.  With mean the mean of
+    bank_rates (the bank's per-trace arrival rates, TraceBank.rate), env b's target load in phase
+    j is mean * (1 + a_b * sin(2 pi (j / phases + phi_b))), a_b uniform in amplitude = (lo, hi),
+    0 <= lo <= hi < 1, phi_b uniform in phase = (lo, hi); the id is that of the bank trace whose
+    rate is nearest to the target (the first of equals).  Deterministic for a seed."""
+    import torch
+
+    P, B = int(phases), int(num_envs)
+    lo, hi = float(amplitude[0]), float(amplitude[1])
+    plo, phi_hi = float(phase[0]), float(phase[1])
+    if P < 1 or B < 1 or not (0.0 <= lo <= hi < 1.0) or not plo <= phi_hi:
+        raise ValueError(f"need phases >= 1, num_envs >= 1, 0 <= lo <= hi < 1 and an ordered "
+                         f"phase range (got {phases}, {num_envs}, {amplitude}, {phase})")
+    rates = torch.as_tensor(np.asarray(bank_rates, np.float64)).reshape(-1)
+    if rates.numel() < 1 or not bool((rates > 0).all()):
+        raise ValueError("bank_rates: need (T,) positive rates")
+    g = torch.Generator().manual_seed(int(seed))
+    amp = lo + (hi - lo) * torch.rand(B, generator=g, dtype=torch.float64)
+    phi = plo + (phi_hi - plo) * torch.rand(B, generator=g, dtype=torch.float64)
+    j = torch.arange(P, dtype=torch.float64) / P
+    target = rates.mean() * (1.0 + amp[:, None] * torch.sin(2.0 * math.pi * (j[None, :] + phi[:, None])))
+    ids = (target[:, :, None] - rates[None, None, :]).abs().argmin(dim=2)
+    return ids.to(device=device, dtype=torch.int32)

@@ -98,9 +98,69 @@ def builtin(name: str = "poisson_for_loop_rate_500") -> Trace:
     return load_npz(os.path.join(DATA, name + ".npz"))
 
 
-def synthetic(rows: int, rate: float, seed: int = 0) -> Trace:
-    """Poisson-times, lognormal-N trace for tests (no file needed)."""
+def synthetic(rows: int, rate: float, seed: int = 0, *, work: str = "lognormal",
+              alpha: float = 1.5, bound: float = 1000.0) -> Trace:
+    """Poisson-times trace for tests (no file needed).  work: the job sizes N -- "lognormal" (the
+    default), or "pareto": bounded Pareto of shape `alpha` on [N_min, bound * N_min], the
+    heavy-tailed sizes of web flows, drawn by inverting its CDF."""
     rng = np.random.default_rng(seed)
     t = np.cumsum(rng.exponential(1.0 / rate, rows))
-    n = np.maximum(1, rng.lognormal(14.8, 0.8, rows)).astype(np.int64)
-    return from_times(t, n, f"synthetic-{rows}-{rate}")
+    if work == "lognormal":
+        n = np.maximum(1, rng.lognormal(14.8, 0.8, rows)).astype(np.int64)
+        return from_times(t, n, f"synthetic-{rows}-{rate}")
+    if work != "pareto":
+        raise ValueError(f"work: 'lognormal' or 'pareto' (got {work!r})")
+    if not (alpha > 0.0 and bound > 1.0):
+        raise ValueError(f"pareto: need alpha > 0 and bound > 1 (got {alpha}, {bound})")
+    lo = 1.0e6
+    u = rng.random(rows)
+    x = lo * (1.0 - u * (1.0 - float(bound) ** -float(alpha))) ** (-1.0 / float(alpha))
+    n = np.maximum(1, x).astype(np.int64)
+    return from_times(t, n, f"synthetic-pareto{alpha:g}-{rows}-{rate}")
+
+
+def rescaled(trace: Trace, factor: float) -> Trace:
+    """The same rows at `factor` times the load: every gap becomes rint(gap / factor), the work is
+    untouched.  A bank of one trace at several loads (TraceBank) is made of these."""
+    f = float(factor)
+    if not (f > 0.0 and np.isfinite(f)):
+        raise ValueError(f"factor: a finite number > 0 (got {factor})")
+    gap = np.rint(trace.gap_us.astype(np.float64) / f)
+    if gap.max() >= 2**31:
+        raise ValueError("trace gaps must be < 2^31 us")
+    return Trace(gap.astype(np.uint32), trace.work.copy(), float(trace.rate * f),
+                 f"{trace.name}-x{f:g}")
+
+
+class TraceBank:
+    """T traces back to back (lbsim_set_trace_bank): trace t is rows
+    [row_begin[t], row_begin[t + 1]) of gap_us / work.  One handle holds a bank; each env replays
+    the trace its id names (VecLoadBalanceEnv.set_env_trace / set_trace_schedule)."""
+
+    MAX_TRACES = 4096
+
+    def __init__(self, traces):
+        traces = [traces] if isinstance(traces, Trace) else list(traces)
+        if not 1 <= len(traces) <= self.MAX_TRACES:
+            raise ValueError(f"a bank holds 1 to {self.MAX_TRACES} traces (got {len(traces)})")
+        if any(t.rows < 1 for t in traces):
+            raise ValueError("every trace of a bank needs at least one row")
+        self.traces = traces
+        self.row_begin = np.zeros(len(traces) + 1, np.int64)
+        np.cumsum([t.rows for t in traces], out=self.row_begin[1:])
+        if self.row_begin[-1] >= 2**31:
+            raise ValueError("a bank holds fewer than 2^31 rows in all")
+        self.gap_us = np.concatenate([np.asarray(t.gap_us, np.uint32) for t in traces])
+        self.work = np.concatenate([np.asarray(t.work, np.float32) for t in traces])
+        self.rate = np.array([t.rate for t in traces], np.float64)
+        self.name = [t.name for t in traces]
+
+    def __len__(self) -> int:
+        return len(self.traces)
+
+    def __getitem__(self, t: int) -> Trace:
+        return self.traces[t]
+
+    @property
+    def rows(self) -> int:
+        return int(self.row_begin[-1])
