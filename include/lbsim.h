@@ -542,6 +542,50 @@ int lbsim_set_trace_schedule(lbsim_t* h, const int32_t* trace_id, int rows, int 
 int lbsim_clear_trace_schedule(lbsim_t* h);
 int lbsim_env_trace(lbsim_t* h, int32_t* trace_id_out, int32_t* phase_out, void* stream);
 
+/* ---- workload tables (per-env gap and flow-size distributions) ----
+ * A Poisson handle draws, for each arrival, a gap -ln(u0) * mean_gap and a work -ln(u1).  With
+ * workload tables in force it looks both up instead: a table is LBSIM_TABLE_BINS f32 quantile
+ * levels of a mean-1 distribution, indexed by the raw 32-bit Philox word v of the draw (small v =
+ * the tail, as for -ln u):
+ *     bin(v) = v for v < 32, else with e = floor(log2 v): 32 (e - 4) + ((v >> (e - 5)) & 31)
+ * (bins 0..31 hold one word each; bin k >= 32 holds 2^(k / 32 - 1) words: 32 levels per octave of
+ * tail probability, down to 2^-32).  The arrival with Philox block d of env b gets
+ *     gap  = max(1, (int32)(table[gap_id[b]][bin(d.x)] * mean_gap_b))   us
+ *     work = table[work_id[b]][bin(d.y)]
+ * with mean_gap_b the env's mean gap exactly as without tables (the config's, lbsim_set_env_rates'
+ * or a schedule's); d.z and d.w are used as before.  A pure lookup: no interpolation.
+ * lbsim_set_workload_tables: tables [T, LBSIM_TABLE_BINS] f32, gap_id / work_id int32 [rows] with
+ * rows = 1 (every env the same pair) or B, all DEVICE pointers; 1 <= T <= 1024.  From the next
+ * launch on (step, reset, warm-up) every arrival drawn uses the tables; the arrival already drawn
+ * keeps its time and work.  The call validates on the device, waits on `stream`, and on any
+ * offender leaves what was in force untouched.  LBSIM_EINVAL: a TRACE handle (the trace supplies
+ * gap and work); T out of range; an id outside [0, T); an entry that is not finite or < 0; a
+ * table some env uses for gaps with an entry > 64 or a mass-weighted mean < 2^-4; a table some env
+ * uses for work whose largest entry wmax breaks  wmax * (1e6 / mu_min) * queue_capacity <= 2^30
+ * (mu_min: the smallest server rate in force: the config's, the per-env arrays' or a schedule's
+ * tables'; this keeps the 32-bit relative times safe).  LBSIM_ESHAPE: rows neither 1 nor B.
+ * While tables are in force lbsim_set_env_rates / lbsim_set_rate_schedule reject a server rate
+ * below wmax * queue_capacity * 1e6 / 2^30 (their lower bound, 1 without tables).
+ * lbsim_set_env_workload: new ids [B] for the bank in force (either NULL = unchanged), validated
+ * the same way; LBSIM_EINVAL without tables.  lbsim_get_env_workload: the ids in force into int32
+ * DEVICE arrays [B] (either NULL); LBSIM_EINVAL without tables.  lbsim_clear_workload_tables: back
+ * to the closed form (the buffers stay allocated).
+ * The first call allocates the bank and the id array; later calls with the same T rewrite both in
+ * place, so a step captured into a hipGraph after the first call sees them on replay; a new T, or
+ * clearing, needs a new capture.  A handle with tables in force is a full handle, as one with flow
+ * statistics: its steps run dynamics_group_full_kernel in two launches, whatever dyn_mapping /
+ * step_kernel ask for (the lookups are compiled into that kernel alone).  lbsim_step / lbsim_reset gain no allocation and no
+ * synchronisation.  Tables and ids are NOT part of the snapshot: a restored or forked env draws
+ * from the tables of the slot it is loaded into.  Draws are keyed by global env id, so a shard
+ * passes its own rows gap_id[lo:hi]. */
+#define LBSIM_TABLE_BINS 896
+int lbsim_set_workload_tables(lbsim_t* h, const float* tables, int n_tables, const int32_t* gap_id,
+                              const int32_t* work_id, int rows, void* stream);
+int lbsim_set_env_workload(lbsim_t* h, const int32_t* gap_id, const int32_t* work_id,
+                           void* stream);
+int lbsim_get_env_workload(lbsim_t* h, int32_t* gap_id_out, int32_t* work_id_out, void* stream);
+int lbsim_clear_workload_tables(lbsim_t* h);
+
 /*
  * Exact flow-completion-time statistics, opt-in per handle.  A handle with
  * them on counts every flow that completes during a STEP of an env, once, with its true

@@ -9,9 +9,15 @@ from .env import (FEATURE_NAMES, DeviceSnapshot, LoadBalanceEnv, LoadBalanceEnvG
 from .multi_agent import MultiAgentLoadBalanceEnv, VecMultiAgentLoadBalanceEnv
 from .randomize import burst_schedule, diurnal_schedule, sample_rates, schedule_phase
 from .spaces import Box, MultiDiscrete
+from .workload import (TABLE_BINS, bounded_pareto_table, constant_table, empirical_table,
+                       exponential_table, hyperexp_table, lognormal_table, quantile_table,
+                       sample_table_ids, table_bin, table_cv2, table_mean, weibull_table)
 
 __all__ = ["FEATURE_NAMES", "LoadBalanceEnv", "LoadBalanceEnvGym", "VecLoadBalanceEnv",
            "MultiAgentLoadBalanceEnv", "VecMultiAgentLoadBalanceEnv", "make_config", "Box",
            "MultiDiscrete", "sample_rates", "schedule_phase", "diurnal_schedule",
-           "burst_schedule", "DeviceSnapshot"]
+           "burst_schedule", "DeviceSnapshot", "TABLE_BINS", "table_bin", "quantile_table",
+           "exponential_table", "bounded_pareto_table", "lognormal_table", "hyperexp_table",
+           "weibull_table", "constant_table", "empirical_table", "table_mean", "table_cv2",
+           "sample_table_ids"]
 __version__ = "0.1.0"

@@ -181,6 +181,10 @@ _SIGNATURES = {
                                                 ctypes.c_int, _P]),
     "lbsim_clear_trace_schedule": (ctypes.c_int, [_P]),
     "lbsim_env_trace": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lbsim_set_workload_tables": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, _P, ctypes.c_int, _P]),
+    "lbsim_set_env_workload": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lbsim_get_env_workload": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lbsim_clear_workload_tables": (ctypes.c_int, [_P]),
     "lbsim_flow_stats_enable": (ctypes.c_int, [_P]),
     "lbsim_flow_stats_get": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "lbsim_flow_stats_quantiles": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),

@@ -92,6 +92,13 @@ struct lbsim {
   float* sched_buf = nullptr;
   int sched_alloc_P = 0;
   int sched_P = 0, sched_H = 0, sched_wrap = 0;
+  // lbsim_set_workload_tables: the block for wtab_alloc_T tables (WorkTabBuf below), moved only by
+  // a call with another T; wtab_T tables in force (0: the closed form) and wtab_wmax, the largest
+  // entry of the tables some env uses for work
+  void* wtab_buf = nullptr;
+  int wtab_alloc_T = 0;
+  int wtab_T = 0;
+  float wtab_wmax = 0.0f;
   // lbsim_flow_stats_enable: one block (sum_us, hist, count, max_us), allocated once, never moved
   void* flow_buf = nullptr;
   FlowStats flow{};  // its arrays (null pointers: statistics off)
@@ -371,16 +378,17 @@ uint32_t* env_rates_bad(const lbsim_t* h) {
 // divided in f64 and rounded once to f32 as derive_params does (so an env given the config's own
 // rates computes the config's bits).  Element (b, s) of either input is in[b * stride + s]: the
 // caller's [B] / [B, S] arrays (strides 1, S) or the config's rates for every env (stride 0).
-// Values outside the config's ranges (NaN included) are counted into *bad.
+// Values outside the config's ranges (NaN included) are counted into *bad.  mu_lo: the lower bound
+// of a server rate, 1 (the config's) or what the workload tables in force ask for (mu_floor).
 __global__ void __launch_bounds__(256)
     env_rates_kernel(const float* arr_in, int64_t arr_stride, const float* srv_in,
-                     int64_t srv_stride, int B, int S, EnvRates out, uint32_t* bad) {
+                     int64_t srv_stride, int B, int S, EnvRates out, uint32_t* bad, float mu_lo) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   uint32_t off = 0u;
   if (srv_in != nullptr && i < (int64_t)B * S) {
     const int64_t b = i / S;
     const float mu = srv_in[b * srv_stride + (i - b * S)];
-    off += (!(mu >= 1.0f) || !(mu <= 1.0e7f)) ? 1u : 0u;
+    off += (!(mu >= mu_lo) || !(mu <= 1.0e7f)) ? 1u : 0u;
     out.server[i] = mu;
     out.scale[i] = (float)(1e6 / (double)mu);
   }
@@ -401,13 +409,13 @@ __global__ void __launch_bounds__(256)
 __global__ void __launch_bounds__(256)
     rate_table_kernel(const float* arr_in, int64_t arr_row, int64_t arr_phase, const float* srv_in,
                       int64_t srv_row, int64_t srv_phase, int B, int P, int S, EnvRates out,
-                      uint32_t* bad) {
+                      uint32_t* bad, float mu_lo) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   uint32_t off = 0u;
   if (i < (int64_t)B * P * S) {
     const int64_t r = i / S, b = r / P;
     const float mu = srv_in[b * srv_row + (r - b * P) * srv_phase + (i - r * S)];
-    off += (!(mu >= 1.0f) || !(mu <= 1.0e7f)) ? 1u : 0u;
+    off += (!(mu >= mu_lo) || !(mu <= 1.0e7f)) ? 1u : 0u;
     out.server[i] = mu;
     out.scale[i] = (float)(1e6 / (double)mu);
   }
@@ -509,6 +517,88 @@ __global__ void __launch_bounds__(256)
   if (phase_out != nullptr) phase_out[b] = (int32_t)phase;
 }
 
+// ---- workload tables (lbsim_set_workload_tables): validation and conversion
+static_assert(kTableBins == LBSIM_TABLE_BINS && kTableBins % 64 == 0,
+              "work_table_kernel: whole passes of one wave");
+constexpr int kMaxWorkTables = 1024;  // ids are 16-bit halves of one word per env
+
+// The ids of a call to one word per env, out[b] = gap_id | work_id << 16.  Element b of either
+// input is in[b * stride] (stride 0: one id for every env); a NULL input keeps the env's id of
+// `cur`, the descriptors in force.  Ids outside [0, T) are counted into *bad; used[t] gets bit 0
+// when some env draws gaps from table t and bit 1 when some env draws work from it.
+__global__ void __launch_bounds__(256)
+    work_ids_kernel(const int32_t* gap_in, int64_t gap_stride, const int32_t* work_in,
+                    int64_t work_stride, const uint32_t* cur, int B, int T, uint32_t* out,
+                    uint32_t* used, uint32_t* bad) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t off = 0u;
+  if (b < (int64_t)B) {
+    const int32_t g = gap_in != nullptr ? gap_in[b * gap_stride] : (int32_t)(cur[b] & 0xFFFFu);
+    const int32_t w = work_in != nullptr ? work_in[b * work_stride] : (int32_t)(cur[b] >> 16);
+    const bool g_ok = g >= 0 && g < T, w_ok = w >= 0 && w < T;
+    off = (g_ok ? 0u : 1u) + (w_ok ? 0u : 1u);
+    if (g_ok) atomicOr(used + g, 1u);
+    if (w_ok) atomicOr(used + w, 2u);
+    out[b] = g_ok && w_ok ? (uint32_t)g | (uint32_t)w << 16 : 0u;
+  }
+  for (int d = 32; d > 0; d >>= 1) off += __shfl_xor(off, d, 64);
+  if ((threadIdx.x & 63) == 0 && off != 0u) atomicAdd(bad, off);
+}
+
+// One wave per table: the entries into `out`, the offenders into res[0] (an entry that is not
+// finite or < 0; in a table used for gaps an entry > 64, or a mass-weighted mean < 2^-4), and the
+// largest entry of the tables used for work into res[1] (f32 bits: entries are >= 0, so the bits
+// order as the values).  The mean weighs bin k with its count of Philox words, summed in f64.
+__global__ void __launch_bounds__(64)
+    work_table_kernel(const float* in, const uint32_t* used, float* out, uint32_t* res) {
+  const int lane = (int)threadIdx.x;
+  const size_t base = (size_t)blockIdx.x * (size_t)kTableBins;
+  const uint32_t use = used[blockIdx.x];
+  uint32_t off = 0u;
+  double m = 0.0;
+  float mx = 0.0f;
+  for (int k = lane; k < kTableBins; k += 64) {
+    const float x = in[base + (size_t)k];
+    const bool ok = x >= 0.0f && x <= 3.402823466e38f;  // false for NaN
+    off += (!ok || ((use & 1u) && x > 64.0f)) ? 1u : 0u;
+    out[base + (size_t)k] = x;
+    m += (double)x * (k < 32 ? 1.0 : (double)(1ull << (k / 32 - 1)));
+    mx = ok && x > mx ? x : mx;
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    off += __shfl_xor(off, d, 64);
+    m += __shfl_xor(m, d, 64);
+    const float o = __shfl_xor(mx, d, 64);
+    mx = o > mx ? o : mx;
+  }
+  if (lane == 0) {
+    if (off == 0u && (use & 1u) && !(m >= 268435456.0)) off = 1u;  // mean < 2^-4 (m is mean * 2^32)
+    if (off != 0u) atomicAdd(res, off);
+    if (use & 2u) atomicMax(res + 1, __float_as_uint(mx));
+  }
+}
+
+// The largest of n positive floats into *out, as f32 bits (the servers' 1e6 / mu in force).
+__global__ void __launch_bounds__(256) scale_max_kernel(const float* x, int64_t n, uint32_t* out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t v = i < n ? __float_as_uint(x[i]) : 0u;
+  for (int d = 32; d > 0; d >>= 1) {
+    const uint32_t o = __shfl_xor(v, d, 64);
+    v = o > v ? o : v;
+  }
+  if ((threadIdx.x & 63) == 0) atomicMax(out, v);
+}
+
+// The descriptors back to ids (lbsim_get_env_workload); either output may be NULL.
+__global__ void __launch_bounds__(256)
+    work_ids_get_kernel(const uint32_t* desc, int B, int32_t* gap_out, int32_t* work_out) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= (int64_t)B) return;
+  const uint32_t d = desc[b];
+  if (gap_out != nullptr) gap_out[b] = (int32_t)(d & 0xFFFFu);
+  if (work_out != nullptr) work_out[b] = (int32_t)(d >> 16);
+}
+
 int launch_check(lbsim_t* h, const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, LBSIM_EDEVICE, "%s: %s", what, hipGetErrorString(e));
@@ -591,7 +681,7 @@ void env_rates_fill_defaults(lbsim_t* h, hipStream_t s) {
   const int64_t n = (int64_t)h->B * h->S;
   hipLaunchKernelGGL(env_rates_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, def,
                      (int64_t)0, def + 1, (int64_t)0, h->B, h->S, env_rates_live(h),
-                     env_rates_bad(h));
+                     env_rates_bad(h), 1.0f);
 }
 
 // The per-env rate block: allocated once, its live arrays holding the config's rates.
@@ -758,6 +848,123 @@ void trace_sel_drop(lbsim_t* h) {
   if (h->prm.trace) set_env_trace(h->st, nullptr);
 }
 
+// ---- workload tables (lbsim_set_workload_tables).  A block for T tables holds
+// the live tables [T * 896] and descriptors [B] (what work_tables / work_ids of DevState point
+// to), their staging copies (a call converts into these and only a valid one is copied over the
+// live ones), used[T] (bit 0: some env's gap table, bit 1: some env's work table) and res[4]:
+// the offender count, the largest work entry and the largest 1e6 / mu in force, as f32 bits.
+struct WorkTabBuf {
+  float* live_tab;
+  uint32_t* live_ids;
+  float* stg_tab;
+  uint32_t *stg_ids, *used, *res;
+};
+size_t work_tab_bytes(const lbsim_t* h, int T) {
+  return 2 * ((size_t)T * kTableBins + (size_t)h->B) * 4 + ((size_t)T + 4) * 4;
+}
+WorkTabBuf work_tab_at(const lbsim_t* h, void* buf, int T) {
+  const size_t n = (size_t)T * kTableBins, B = (size_t)h->B;
+  WorkTabBuf w;
+  w.live_tab = (float*)buf;
+  w.live_ids = (uint32_t*)(w.live_tab + n);
+  w.stg_tab = (float*)(w.live_ids + B);
+  w.stg_ids = (uint32_t*)(w.stg_tab + n);
+  w.used = w.stg_ids + B;
+  w.res = w.used + T;
+  return w;
+}
+// The bound that keeps the 32-bit relative times safe with work tables: wmax * (1e6 / mu) * Q <=
+// 2^30 for every server (without tables the worst case is 16.64 * 1e6 * 64 < 2^30).
+constexpr double kWorkTimeBound = 1073741824.0;
+// The lower bound of a server rate that lbsim_set_env_rates / lbsim_set_rate_schedule accept: 1,
+// or what the work tables in force ask for (rounded up, with a margin for the f32 division that
+// makes 1e6 / mu, so a rate accepted here passes the tables' own check later).
+float mu_floor(const lbsim_t* h) {
+  if (h->wtab_T == 0) return 1.0f;
+  const double lo = (double)h->wtab_wmax * (double)h->Q * 1e6 / kWorkTimeBound * (1.0 + 1e-6);
+  return lo > 1.0 ? (float)lo : 1.0f;
+}
+
+// The common body of lbsim_set_workload_tables and lbsim_set_env_workload: T tables at `tables`
+// (the caller's, or the live ones) and ids (element b at in[b * stride]; NULL: the id in force)
+// validated into the staging arrays of the block for T tables, then copied over the live ones.
+int work_tables_apply(lbsim_t* h, const float* tables, int T, const int32_t* gap_id,
+                      int64_t gap_stride, const int32_t* work_id, int64_t work_stride,
+                      hipStream_t s) {
+  const size_t B = (size_t)h->B, n = (size_t)T * kTableBins;
+  void* buf = h->wtab_buf;
+  const bool fresh = buf == nullptr || h->wtab_alloc_T != T;
+  if (fresh) {
+    const size_t bytes = work_tab_bytes(h, T);
+    if (hipMalloc(&buf, bytes) != hipSuccess)
+      return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", bytes);
+  }
+  auto give_up = [&](int code, const char* fmt, double a = 0.0, double b = 0.0, double c = 0.0) {
+    if (fresh) (void)hipFree(buf);  // (waits for the device)
+    return fail(h, code, fmt, a, b, c);
+  };
+  const WorkTabBuf w = work_tab_at(h, buf, T);
+  const uint32_t* const cur =
+      h->wtab_T > 0 ? work_tab_at(h, h->wtab_buf, h->wtab_alloc_T).live_ids : nullptr;
+  if (hipMemsetAsync(w.used, 0, ((size_t)T + 4) * 4, s) != hipSuccess)
+    return give_up(LBSIM_EDEVICE, "workload tables: hipMemsetAsync failed");
+  hipLaunchKernelGGL(work_ids_kernel, dim3(blocks256(B)), dim3(256), 0, s, gap_id, gap_stride,
+                     work_id, work_stride, cur, h->B, T, w.stg_ids, w.used, w.res);
+  hipLaunchKernelGGL(work_table_kernel, dim3((unsigned)T), dim3(64), 0, s, tables,
+                     (const uint32_t*)w.used, w.stg_tab, w.res);
+  // the largest 1e6 / mu in force: a schedule's tables, the per-env arrays, or the config's
+  double scale_max = 0.0;
+  if (h->sched_P > 0) {
+    const size_t NS = B * (size_t)h->sched_P * (size_t)h->S;
+    hipLaunchKernelGGL(scale_max_kernel, dim3(blocks256(NS)), dim3(256), 0, s,
+                       (const float*)sched_live(h, h->sched_buf, h->sched_P).scale, (int64_t)NS,
+                       w.res + 2);
+  } else if (h->rates_on) {
+    const size_t BS = B * (size_t)h->S;
+    hipLaunchKernelGGL(scale_max_kernel, dim3(blocks256(BS)), dim3(256), 0, s,
+                       (const float*)env_rates_live(h).scale, (int64_t)BS, w.res + 2);
+  } else {
+    for (int k = 0; k < h->S; ++k)
+      scale_max = h->prm.svc_scale[k] > scale_max ? h->prm.svc_scale[k] : scale_max;
+  }
+  if (launch_check(h, "work_table_kernel") != LBSIM_OK) {
+    if (fresh) (void)hipFree(buf);
+    return LBSIM_EDEVICE;
+  }
+  uint32_t res[4] = {0u, 0u, 0u, 0u};
+  if (hipMemcpyAsync(res, w.res, sizeof(res), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return give_up(LBSIM_EDEVICE, "workload tables: validation failed");
+  if (res[0] != 0u)  // nothing live was touched: what was in force stays in force
+    return give_up(LBSIM_EINVAL,
+                   "workload tables: %.0f offender(s): ids must be in [0, %.0f), entries finite and "
+                   ">= 0, a table used for gaps <= 64 with a mass-weighted mean >= 1/16",
+                   (double)res[0], (double)T);
+  float wmax, smax;
+  memcpy(&wmax, &res[1], 4);
+  memcpy(&smax, &res[2], 4);
+  if (scale_max == 0.0) scale_max = (double)smax;
+  if ((double)wmax * scale_max * (double)h->Q > kWorkTimeBound)
+    return give_up(LBSIM_EINVAL,
+                   "workload tables: the largest work entry %g breaks wmax * (1e6 / mu_min) * "
+                   "queue_capacity <= 2^30 (mu_min = %g flows/s, queue_capacity = %.0f)",
+                   (double)wmax, 1e6 / scale_max, (double)h->Q);
+  bool ok = true;
+  if (tables != w.live_tab)
+    ok &= hipMemcpyAsync(w.live_tab, w.stg_tab, n * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  ok &= hipMemcpyAsync(w.live_ids, w.stg_ids, B * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  if (!ok) return give_up(LBSIM_EDEVICE, "workload tables: device copy failed");
+  if (fresh) {
+    if (h->wtab_buf != nullptr) (void)hipFree(h->wtab_buf);  // (waits for the device)
+    h->wtab_buf = buf;
+    h->wtab_alloc_T = T;
+  }
+  set_work_tables(h->st, w.live_tab, w.live_ids);
+  h->wtab_T = T;
+  h->wtab_wmax = wmax;
+  return LBSIM_OK;
+}
+
 // Brackets one launch with profiler events when profiling is on (class: see lbsim.h).
 struct ProfScope {
   lbsim_t* h;
@@ -844,6 +1051,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.split = p.split != 0, in.res_vpp = p.res_vpp != 0, in.dur_plane = dur_plane(p);
   in.next_reset = p.next_reset != 0;
   in.flow_stats = h->flow.hist != nullptr;
+  in.work_tables = h->wtab_T > 0;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -1023,6 +1231,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->rates_buf) (void)hipFree(h->rates_buf);
     if (h->sched_buf) (void)hipFree(h->sched_buf);
     if (h->flow_buf) (void)hipFree(h->flow_buf);
+    if (h->wtab_buf) (void)hipFree(h->wtab_buf);
     for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
   }
   delete h;
@@ -1386,6 +1595,62 @@ int lbsim_env_trace(lbsim_t* h, int32_t* trace_id_out, int32_t* phase_out, void*
   return launch_check(h, "trace_gather_kernel");
 }
 
+int lbsim_set_workload_tables(lbsim_t* h, const float* tables, int n_tables, const int32_t* gap_id,
+                              const int32_t* work_id, int rows, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->prm.trace)
+    return fail(h, LBSIM_EINVAL, "workload tables on a TRACE handle: the trace supplies gap and "
+                                 "work");
+  if (tables == nullptr || gap_id == nullptr || work_id == nullptr)
+    return fail(h, LBSIM_EINVAL, "workload tables: tables, gap_id and work_id must not be NULL");
+  if (n_tables < 1 || n_tables > kMaxWorkTables)
+    return fail(h, LBSIM_EINVAL, "workload tables: n_tables must be in [1, %d] (got %d)",
+                kMaxWorkTables, n_tables);
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "workload tables: rows must be 1 or num_envs = %d (got %d)", h->B,
+                rows);
+  DeviceGuard g(h->device);
+  const int64_t stride = rows == 1 ? 0 : 1;
+  const int rc = work_tables_apply(h, tables, n_tables, gap_id, stride, work_id, stride,
+                                   (hipStream_t)stream);
+  // a handle with tables is a full handle (make_plan): its steps and resets run
+  // dynamics_group_full_kernel, the one kernel that carries the lookups
+  if (rc == LBSIM_OK) h->plan = plan_of(h);
+  return rc;
+}
+
+int lbsim_set_env_workload(lbsim_t* h, const int32_t* gap_id, const int32_t* work_id,
+                           void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->wtab_T == 0)
+    return fail(h, LBSIM_EINVAL, "env workload: no workload tables in force "
+                                 "(lbsim_set_workload_tables first)");
+  if (gap_id == nullptr && work_id == nullptr) return LBSIM_OK;
+  DeviceGuard g(h->device);
+  return work_tables_apply(h, work_tab_at(h, h->wtab_buf, h->wtab_T).live_tab, h->wtab_T, gap_id,
+                           1, work_id, 1, (hipStream_t)stream);
+}
+
+int lbsim_get_env_workload(lbsim_t* h, int32_t* gap_id_out, int32_t* work_id_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->wtab_T == 0) return fail(h, LBSIM_EINVAL, "env workload: no workload tables in force");
+  if (gap_id_out == nullptr && work_id_out == nullptr) return LBSIM_OK;
+  DeviceGuard g(h->device);
+  hipLaunchKernelGGL(work_ids_get_kernel, dim3(blocks256((size_t)h->B)), dim3(256), 0,
+                     (hipStream_t)stream, work_ids(h->st), h->B, gap_id_out, work_id_out);
+  return launch_check(h, "work_ids_get_kernel");
+}
+
+int lbsim_clear_workload_tables(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->prm.trace) return LBSIM_OK;  // (never had any: its two words are the trace)
+  set_work_tables(h->st, nullptr, nullptr);
+  h->wtab_T = 0;
+  h->wtab_wmax = 0.0f;
+  h->plan = plan_of(h);  // back to the kernels of a handle without tables
+  return LBSIM_OK;
+}
+
 int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* server_rate,
                         void* stream) {
   if (h == nullptr) return LBSIM_EINVAL;
@@ -1397,6 +1662,10 @@ int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* serv
     return fail(h, LBSIM_ENOTSUP, "per-env arrival rates on a TRACE handle: the trace sets the "
                                   "arrival rate (per-env server rates are allowed)");
   if (arrival_rate == nullptr && server_rate == nullptr) return LBSIM_OK;
+  if (server_rate == nullptr && h->sched_P > 0 && h->wtab_T > 0)
+    return fail(h, LBSIM_EINVAL, "per-env rates: on a handle with workload tables and a rate "
+                                 "schedule, give server_rate too (dropping the schedule would "
+                                 "bring back server rates the tables were not checked against)");
   DeviceGuard g(h->device);
   const hipStream_t s = (hipStream_t)stream;
   int rc = env_rates_ensure(h, s);
@@ -1404,10 +1673,12 @@ int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* serv
   const size_t B = (size_t)h->B, BS = B * h->S;
   const EnvRates live = env_rates_live(h), stg = env_rates_staging(h);
   uint32_t* const bad = env_rates_bad(h);
+  const float mu_lo = mu_floor(h);
   if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess)
     return fail(h, LBSIM_EDEVICE, "per-env rates: hipMemsetAsync failed");
   hipLaunchKernelGGL(env_rates_kernel, dim3((unsigned)((BS + 255) / 256)), dim3(256), 0, s,
-                     arrival_rate, (int64_t)1, server_rate, (int64_t)h->S, h->B, h->S, stg, bad);
+                     arrival_rate, (int64_t)1, server_rate, (int64_t)h->S, h->B, h->S, stg, bad,
+                     mu_lo);
   rc = launch_check(h, "env_rates_kernel");
   if (rc != LBSIM_OK) return rc;
   uint32_t nbad = 0;
@@ -1416,7 +1687,8 @@ int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* serv
     return fail(h, LBSIM_EDEVICE, "per-env rates: conversion failed");
   if (nbad != 0u)  // the live arrays are untouched: the previous rates stay in force
     return fail(h, LBSIM_EINVAL, "per-env rates: %u value(s) out of range (arrival_rate must be in "
-                                 "[0.1, 1e6] flows/s, server_rate in [1, 1e7]; NaN rejected)", nbad);
+                                 "[0.1, 1e6] flows/s, server_rate in [%g, 1e7]; NaN rejected)", nbad,
+                (double)mu_lo);
   sched_drop(h);  // (a scheduled handle: back to its per-env arrays first)
   bool ok = true;
   if (arrival_rate != nullptr) {
@@ -1435,6 +1707,16 @@ int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* serv
 
 int lbsim_clear_env_rates(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  {  // work tables in force were validated against the rates being dropped: the config's own
+     // server rates must satisfy their floor too
+    const float mu_lo = mu_floor(h);
+    for (int k = 0; k < h->S; ++k)
+      if (h->cfg.server_rate[k] < mu_lo)
+        return fail(h, LBSIM_EINVAL, "clearing the rates: the config's server_rate[%d] = %g is "
+                                     "below %g, the floor of the workload tables in force (clear "
+                                     "or replace the tables first)", k,
+                    (double)h->cfg.server_rate[k], (double)mu_lo);
+  }
   sched_drop(h);
   h->rates_on = false;
   set_env_arrays(h, nullptr, nullptr);
@@ -1523,13 +1805,14 @@ int lbsim_set_rate_schedule(lbsim_t* h, const float* arrival_rate, const float* 
   if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess)
     return give_up(LBSIM_EDEVICE, "hipMemsetAsync failed");
   const int64_t per_row = rows == 1 ? 0 : 1;  // one shared schedule: every env reads row 0
+  const float mu_lo = mu_floor(h);
   const float* const arr_in = arrival_rate != nullptr ? arrival_rate : base;
   const float* const srv_in = server_rate != nullptr ? server_rate : base + B;
   hipLaunchKernelGGL(rate_table_kernel, dim3(blocks256(NS)), dim3(256), 0, s, arr_in,
                      arrival_rate != nullptr ? per_row * P : (int64_t)1,
                      (int64_t)(arrival_rate != nullptr ? 1 : 0), srv_in,
                      server_rate != nullptr ? per_row * P * S : (int64_t)S,
-                     (int64_t)(server_rate != nullptr ? S : 0), h->B, P, S, stg, bad);
+                     (int64_t)(server_rate != nullptr ? S : 0), h->B, P, S, stg, bad, mu_lo);
   if (launch_check(h, "rate_table_kernel") != LBSIM_OK) {
     if (fresh) (void)hipFree(buf);
     return LBSIM_EDEVICE;
@@ -1541,7 +1824,8 @@ int lbsim_set_rate_schedule(lbsim_t* h, const float* arrival_rate, const float* 
   if (nbad != 0u) {  // nothing live was touched: the previous schedule or rates stay in force
     if (fresh) (void)hipFree(buf);
     return fail(h, LBSIM_EINVAL, "rate schedule: %u value(s) out of range (arrival_rate must be in "
-                                 "[0.1, 1e6] flows/s, server_rate in [1, 1e7]; NaN rejected)", nbad);
+                                 "[0.1, 1e6] flows/s, server_rate in [%g, 1e7]; NaN rejected)", nbad,
+                (double)mu_lo);
   }
   // staging over the live tables (the two halves are contiguous: one copy)
   if (hipMemcpyAsync(live.arrival, stg.arrival, 2 * (N + NS) * sizeof(float),
@@ -1563,6 +1847,8 @@ int lbsim_set_rate_schedule(lbsim_t* h, const float* arrival_rate, const float* 
 
 int lbsim_clear_rate_schedule(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  for (int k = 0; k < h->S; ++k)  // (as lbsim_clear_env_rates, before anything is dropped)
+    if (h->cfg.server_rate[k] < mu_floor(h)) return lbsim_clear_env_rates(h);
   sched_drop(h);
   if (h->sched_buf != nullptr) {
     // a step captured into a graph while the schedule was set keeps reading the tables: they take
@@ -1575,7 +1861,8 @@ int lbsim_clear_rate_schedule(lbsim_t* h) {
     const int P = h->sched_alloc_P;
     hipLaunchKernelGGL(rate_table_kernel, dim3(blocks256((size_t)h->B * P * h->S)), dim3(256), 0,
                        nullptr, def, (int64_t)0, (int64_t)0, def + 1, (int64_t)0, (int64_t)0, h->B,
-                       P, h->S, sched_live(h, h->sched_buf, P), sched_bad(h, h->sched_buf, P));
+                       P, h->S, sched_live(h, h->sched_buf, P), sched_bad(h, h->sched_buf, P),
+                       1.0f);
     rc = launch_check(h, "rate_table_kernel");
     if (rc != LBSIM_OK) return rc;
   }

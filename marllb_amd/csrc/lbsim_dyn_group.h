@@ -286,15 +286,17 @@ __device__ __forceinline__ GroupConst group_const(const SimParams& p, float mean
 // (profiles/r06i/) -- the plain kernel shed the full handles' code, so the hoisted keys fit.
 // FULL: the handle's features beyond the plain simulator -- n_flow_on_mode VPP's lost-flow counts,
 // a duration plane (duration_mode SERVICE), lost-FIN deferral (split reservoirs), reservoir_mode
-// VPP, exact flow statistics (fs_on) -- compiled only into dynamics_group_full_kernel, so none of their registers weigh on the
-// plain kernel (126 VGPRs, 4 waves per SIMD; with them inlined it took 164).
+// VPP, exact flow statistics (fs_on), workload tables (ws) -- compiled only into
+// dynamics_group_full_kernel, so none of their registers weigh on the plain kernel (126 VGPRs, 4
+// waves per SIMD; with them inlined it took 164).
 template <int G, int POLICY, bool TRACE, bool FAST, bool FULL = false>
 __device__ __forceinline__ void group_event_loop(const DevState& st, const SimParams& p,
                                                  LaneState<1>& E, SrvLane& V, int s, int gbase,
                                                  int n_alias, const GroupConst& gc, int2* win,
                                                  int32_t* atab, int4* acache, uint2* const my_res,
                                                  int2* const my_ring, bool fs_on = false,
-                                                 const TraceSel& ts = TraceSel{}) {
+                                                 const TraceSel& ts = TraceSel{},
+                                                 const WorkSel& ws = WorkSel{}) {
   constexpr int WL = kGroupWL;
   constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
   constexpr bool alias = POLICY == kPolicyAlias;
@@ -341,6 +343,9 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
         while (r >= rows) r -= rows;
         gap = (int32_t)st.trace_gap[ts.base + r];
         wk = st.trace_work[ts.base + r];
+      } else if (FULL && ws.tab != nullptr) {  // wave-uniform: the workload tables (a table
+        // handle is a full one); the lookups sit with the draw, up to G arrivals ahead of their use
+        table_arrival(ws, d.x, d.y, gc.mean_gap, gap, wk);
       } else {  // (the two logs as one packed-f32 polynomial measured 2 % slower: r05t)
         gap = (int32_t)(-lb_logf(u01_open0(d.x)) * gc.mean_gap);
         wk = -lb_logf(u01_open0(d.y));
@@ -630,19 +635,21 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
   //      SED2 scores can only be NaN when some den is 0 / inf / NaN: a wave whose servers all have
   //      finite scores runs the loop without the NaN fallbacks (a wave-uniform choice).
   const GroupConst gc = group_const(p, env_mean_gap(st, p, b), base_ms, base_rem);
+  WorkSel ws{};  // a full Poisson handle: the env's workload tables, if it has any
+  if constexpr (FULL && !TRACE) ws = env_work_sel(st, b);
   const bool finite = lsq || alias || !V.act ||
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
     group_event_loop<G, POLICY, TRACE, false, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                                    acache, my_res, my_ring, fs_on, ts);
+                                                    acache, my_res, my_ring, fs_on, ts, ws);
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
   } else if (__all(finite)) {
     group_event_loop<G, POLICY, TRACE, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                             acache, my_res, my_ring, false, ts);
+                                             acache, my_res, my_ring, false, ts, ws);
   } else {
     group_event_loop<G, POLICY, TRACE, false>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                              acache, my_res, my_ring, false, ts);
+                                              acache, my_res, my_ring, false, ts, ws);
   }
 
   // ---- rebase to the next step's start (this lane's server)
@@ -745,7 +752,9 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     E.clock = 0u;
     E.dropped = 0u;
     E.arr_idx = 0u;
-    draw_arrival<1, TRACE>(st, p, E, b, 0, ts);
+    WorkSel ws{};  // a full Poisson handle: the env's workload tables, if it has any
+    if constexpr (FULL && !TRACE) ws = env_work_sel(st, b);
+    draw_arrival<1, TRACE>(st, p, E, b, 0, ts, ws);
     V.cnt = 0;
     V.head_tc = 0;
     V.head = 0;

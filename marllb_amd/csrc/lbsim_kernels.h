@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "lbsim_math.h"
+#include "lbsim_table.h"
 
 namespace lbk {
 
@@ -93,6 +94,11 @@ struct DevState {
   double* norm_std;
   // arrival trace (TRACE source; nullptr otherwise): us gap before each row, mean-1 work of each
   // row.  A bank (lbsim_set_trace_bank) holds its traces back to back in these two arrays.
+  // A Poisson handle replays no trace, so there the two words carry the workload tables instead
+  // (lbsim_set_workload_tables): work_tables(st), [T][kTableBins] quantile levels
+  // (nullptr = the closed form -ln u), and work_ids(st), [B] gap_id | work_id << 16.  Read by the
+  // Poisson instantiations of dynamics_group_full_kernel alone: the descriptor once, in their
+  // prologue.
   const uint32_t* trace_gap;
   const float* trace_work;
   // per-env workload (lbsim_set_env_rates; nullptr = the shared SimParams::mean_gap_us /
@@ -114,6 +120,16 @@ __host__ __device__ inline const uint2* env_trace(const DevState& st) {
 }
 inline void set_env_trace(DevState& st, const uint2* desc) {
   st.env_gap = reinterpret_cast<const float*>(desc);
+}
+
+// A Poisson handle's workload tables (DevState::trace_work's and trace_gap's words, which such a
+// handle never reads as a trace): the pointers are taken as they are, never the values behind them
+// converted.
+__host__ __device__ inline const float* work_tables(const DevState& st) { return st.trace_work; }
+__host__ __device__ inline const uint32_t* work_ids(const DevState& st) { return st.trace_gap; }
+inline void set_work_tables(DevState& st, const float* tables, const uint32_t* ids) {
+  st.trace_work = tables;
+  st.trace_gap = ids;
 }
 
 // Exact flow statistics (lbsim_flow_stats_enable; nullptr = off), cumulative over
@@ -564,13 +580,44 @@ __device__ __forceinline__ float env_mean_gap(const DevState& st, const SimParam
   return st.env_gap != nullptr ? st.env_gap[b] : p.mean_gap_us;
 }
 
+// The workload tables of env b (a Poisson handle): the bank, nullptr for the closed form, and the
+// env's ids (gap_id | work_id << 16).  A wave-uniform null test, made once in the prologue of a
+// Poisson instantiation of dynamics_group_full_kernel: a handle with tables is a full handle
+// (make_plan), so no other kernel carries the test or the word.
+struct WorkSel {
+  const float* tab;
+  uint32_t ids;
+};
+__device__ __forceinline__ WorkSel env_work_sel(const DevState& st, uint32_t b) {
+  WorkSel w{work_tables(st), 0u};
+  if (w.tab != nullptr) w.ids = work_ids(st)[b];
+  return w;
+}
+// The table rule (w.tab != nullptr): the gap and the work of the arrival whose Philox words are
+// dx, dy.  Two loads at unrelated addresses per lane, each inside a 3.5 KiB table that the cache
+// holds; every draw site issues them where it draws (an arrival or more ahead of the use), never
+// where it consumes.  The gap is at least 1 us, so no table stalls an event loop.
+__device__ __forceinline__ void table_arrival(const WorkSel& w, uint32_t dx, uint32_t dy,
+                                              float mean_gap_us, int32_t& gap, float& work) {
+  const float g = w.tab[(w.ids & 0xFFFFu) * (uint32_t)kTableBins + (uint32_t)table_bin(dx)];
+  work = w.tab[(w.ids >> 16) * (uint32_t)kTableBins + (uint32_t)table_bin(dy)];
+  const int32_t gi = (int32_t)(g * mean_gap_us);
+  gap = gi < 1 ? 1 : gi;
+}
+
 // Arrival draw for one arrival index: gap to it, its work, its two hash words.
 __device__ __forceinline__ void arrival_from_draw(float mean_gap_us, const u32x4& d,
                                                   int32_t t_prev, int32_t& next_arr,
-                                                  float& work, uint32_t& u2, uint32_t& u3) {
-  const int32_t gap = (int32_t)(-lb_logf(u01_open0(d.x)) * mean_gap_us);
+                                                  float& work, uint32_t& u2, uint32_t& u3,
+                                                  const WorkSel& ws = WorkSel{}) {
+  int32_t gap;
+  if (ws.tab != nullptr) {
+    table_arrival(ws, d.x, d.y, mean_gap_us, gap, work);
+  } else {
+    gap = (int32_t)(-lb_logf(u01_open0(d.x)) * mean_gap_us);
+    work = -lb_logf(u01_open0(d.y));
+  }
   next_arr = t_prev + gap;
-  work = -lb_logf(u01_open0(d.y));
   u2 = d.z;
   u3 = d.w;
 }
@@ -579,7 +626,8 @@ __device__ __forceinline__ void arrival_from_draw(float mean_gap_us, const u32x4
 template <int MAXS, bool TRACE = false>
 __device__ __forceinline__ void draw_arrival(const DevState& st, const SimParams& p,
                                              LaneState<MAXS>& L, uint32_t b, int32_t t_prev,
-                                             const TraceSel& ts = TraceSel{}) {
+                                             const TraceSel& ts = TraceSel{},
+                                             const WorkSel& ws = WorkSel{}) {
   const u32x4 d = philox4x32_10(u32x4{L.arr_idx, L.gid, L.episode, kStreamArrival << 24},
                                 p.key0, p.key1);
   if constexpr (TRACE) {
@@ -595,7 +643,8 @@ __device__ __forceinline__ void draw_arrival(const DevState& st, const SimParams
     L.u2 = d.z;
     L.u3 = d.w;
   } else {
-    arrival_from_draw(env_mean_gap(st, p, b), d, t_prev, L.next_arr, L.next_work, L.u2, L.u3);
+    arrival_from_draw(env_mean_gap(st, p, b), d, t_prev, L.next_arr, L.next_work, L.u2, L.u3,
+                      ws);
   }
 }
 

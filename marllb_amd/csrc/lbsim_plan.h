@@ -42,7 +42,8 @@ struct Overrides {
   }
 };
 
-// What the plan depends on: all of it fixed when the handle is created.
+// What the plan depends on: fixed when the handle is created, but for flow_stats (set before the
+// first reset) and work_tables (the plan is made again when tables come into force or are cleared).
 struct PlanInput {
   int B, S, Q;
   int policy;       // lbsim_assign_policy
@@ -57,6 +58,7 @@ struct PlanInput {
   int step_kernel;  // lbsim_step_kernel
   int simds;        // SIMDs of the device (CUs x 4)
   bool flow_stats;  // exact flow statistics are on (lbsim_flow_stats_enable)
+  bool work_tables;  // workload tables are in force (lbsim_set_workload_tables)
 };
 
 enum StepForm { kStepWave, kStepGroupFused, kStepTwoLaunch };
@@ -112,7 +114,9 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
   // Flow statistics are accumulated by the lane that owns a server for the whole launch (no
   // atomics, bitwise reproducible): only the server-per-lane kernel's full form has that code, so
   // a statistics handle plans exactly as a reservoir_mode VPP one does.
-  const bool full_only = in.res_vpp || in.flow_stats;
+  // Workload tables: their lookups are compiled into the full form alone (the runtime test in the
+  // shared instantiations moved the headline kernel's registers).
+  const bool full_only = in.res_vpp || in.flow_stats || in.work_tables;
   const bool wave_fits = ov.dyn_wave != 0 && !ov.group_lanes_set &&
                          in.dyn_mapping != LBSIM_DYN_ENV_PER_LANE && S <= 8 && in.Q <= 32 &&
                          in.policy != LBSIM_POLICY_ALIAS && !in.fail && !in.leak && !in.split &&

@@ -357,6 +357,39 @@ class Handle:
                                                 ctypes.c_void_p(self._stream())))
         return arrival, server
 
+    def set_workload_tables(self, tables, gap_id, work_id) -> None:
+        """Workload tables (lbsim_set_workload_tables): tables (T, 896) f32, gap_id / work_id
+        (rows,) int32, rows = 1 or B, contiguous tensors on the handle's device."""
+        self.check(self.lib.lbsim_set_workload_tables(
+            self.h, ctypes.c_void_p(tables.data_ptr()), int(tables.shape[0]),
+            ctypes.c_void_p(gap_id.data_ptr()), ctypes.c_void_p(work_id.data_ptr()),
+            int(gap_id.shape[0]), ctypes.c_void_p(self._stream())))
+
+    def set_env_workload(self, gap_id=None, work_id=None) -> None:
+        """New table ids (B,) int32 for the bank in force (lbsim_set_env_workload); None leaves
+        that one as it is."""
+        self.check(self.lib.lbsim_set_env_workload(
+            self.h, ctypes.c_void_p(gap_id.data_ptr() if gap_id is not None else None),
+            ctypes.c_void_p(work_id.data_ptr() if work_id is not None else None),
+            ctypes.c_void_p(self._stream())))
+
+    def env_workload(self):
+        """(gap_id (B,), work_id (B,)) int32 device tensors: the table ids in force
+        (lbsim_get_env_workload)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        B = int(self.cfg.num_envs)
+        gap = torch.empty(B, dtype=torch.int32, device=dev)
+        work = torch.empty(B, dtype=torch.int32, device=dev)
+        self.check(self.lib.lbsim_get_env_workload(self.h, ctypes.c_void_p(gap.data_ptr()),
+                                                   ctypes.c_void_p(work.data_ptr()),
+                                                   ctypes.c_void_p(self._stream())))
+        return gap, work
+
+    def clear_workload_tables(self) -> None:
+        """Back to the closed form (lbsim_clear_workload_tables)."""
+        self.check(self.lib.lbsim_clear_workload_tables(self.h))
+
     def enable_flow_stats(self) -> None:
         """Exact per-(env, server) flow statistics from now on (lbsim_flow_stats_enable): before
         the handle's first reset (ValueError after it); a second call is a no-op."""
@@ -890,6 +923,74 @@ class VecLoadBalanceEnv:
         """(B,) int32 device tensor: the trace-schedule phase each env's next step will use."""
         return self.handle.env_trace()[1]
 
+    def _table_ids_arg(self, ids, name, allow_scalar):
+        """Table ids as a contiguous int32 tensor on the env's device: (B,), or with allow_scalar
+        one int for every env, (1,)."""
+        torch = _torch()
+        t = torch.as_tensor(ids)
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError(f"{name}: table ids are integers (got {t.dtype})")
+        if allow_scalar and t.dim() == 0:
+            t = t.reshape(1)
+        elif t.dim() != 1 or t.shape[0] != self.num_envs:
+            raise ValueError(f"{name}: expected {'an int or ' if allow_scalar else ''}"
+                             f"({self.num_envs},), got {tuple(t.shape)}")
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def set_workload_tables(self, tables, gap_id, work_id) -> None:
+        """Per-env arrival-gap and flow-size distributions for a Poisson env
+        (marllb_amd.workload builds the tables): tables is (T, 896), 1 <= T <= 1024, mean-1
+        quantile tables; gap_id and work_id name each env's gap and work table, an int for every
+        env or (B,), arrays or tensors on any device.  From the next launch on (step, reset,
+        warm-up) env b draws gap = max(1 us, tables[gap_id[b]][bin] * its mean gap) and work =
+        tables[work_id[b]][bin] from the Philox words it already draws, in place of -ln u; the
+        arrival already drawn keeps its time and work.  The mean gap is the one in force
+        (make_config's, set_rates', a schedule's), so tables compose with per-env rates, rate
+        schedules, lost FINs, failures, flow statistics, snapshots and shards (a shard passes its
+        own rows, ids[lo:hi]).  A table is a staircase: 32 levels per octave of tail probability.
+        ValueError (what was in force stays): a trace= env, an id outside [0, T), an entry that is
+        not finite or negative, a gap table with an entry above 64 or a mean below 1/16, a work
+        table whose largest entry wmax breaks wmax * 1e6 / mu_min * queue_capacity <= 2^30.
+        While tables are in force set_rates / set_rate_schedule reject server rates below that
+        bound.  Not part of get_state(): a restored env draws from the tables of its slot.
+        A handle with tables runs the full form of the dynamics kernel.
+        graph_mode: the first call must precede the capture; later calls with the same T rewrite
+        the tables and ids in place and replays see them; a new T, or clearing, needs a new
+        capture."""
+        torch = _torch()
+        t = torch.as_tensor(tables)
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if t.dim() != 2 or t.shape[1] != 896:
+            raise ValueError(f"set_workload_tables: tables must be (T, 896), got "
+                             f"{tuple(torch.as_tensor(tables).shape)}")
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        g = self._table_ids_arg(gap_id, "gap_id", True)
+        w = self._table_ids_arg(work_id, "work_id", True)
+        if g.shape[0] != w.shape[0]:  # one shared, one per env: expand the shared one
+            g = g.expand(self.num_envs).contiguous()
+            w = w.expand(self.num_envs).contiguous()
+        self.handle.set_workload_tables(t, g, w)
+
+    def set_env_workload(self, gap_id=None, work_id=None) -> None:
+        """New per-env table ids (B,) for the tables in force; None leaves that one as it is.
+        Validated as set_workload_tables validates (the tables some env now uses for gaps or for
+        work are checked again); ValueError leaves the ids in force untouched
+        (marllb_amd.workload.sample_table_ids draws such ids)."""
+        g = self._table_ids_arg(gap_id, "gap_id", False) if gap_id is not None else None
+        w = self._table_ids_arg(work_id, "work_id", False) if work_id is not None else None
+        self.handle.set_env_workload(g, w)
+
+    @property
+    def env_workload(self):
+        """(gap_id (B,), work_id (B,)) int32 device tensors: the table ids in force (ValueError
+        without tables)."""
+        return self.handle.env_workload()
+
+    def clear_workload_tables(self) -> None:
+        """Back to the closed form: exponential gaps and work."""
+        self.handle.clear_workload_tables()
+
     def flow_stats(self, per_server: bool = False, hist: bool = False) -> Dict[str, Any]:
         """The exact flow statistics since the last clear, as device tensors of shape (B,) or,
         per_server, (B, S): count (int64), mean_s (f64, sum_us / count * 1e-6, 0 where no flow
@@ -1396,6 +1497,30 @@ class LoadBalanceEnv:
 
     def clear_flow_stats(self) -> None:
         self._flow_vec().clear_flow_stats()
+
+    # ---- workload tables (VecLoadBalanceEnv.set_workload_tables of the one env)
+    def _work_vec(self) -> "VecLoadBalanceEnv":
+        if self._vec is None:
+            raise RuntimeError("workload tables need the GPU simulator (not reference_plumbing)")
+        return self._vec
+
+    def set_workload_tables(self, tables, gap_id: int = 0, work_id: int = 0) -> None:
+        """The env's gap and flow-size distributions: tables (T, 896) from marllb_amd.workload,
+        and which of them it draws gaps and work from (VecLoadBalanceEnv.set_workload_tables)."""
+        self._work_vec().set_workload_tables(tables, int(gap_id), int(work_id))
+
+    def set_env_workload(self, gap_id: Optional[int] = None, work_id: Optional[int] = None) -> None:
+        self._work_vec().set_env_workload(None if gap_id is None else [int(gap_id)],
+                                          None if work_id is None else [int(work_id)])
+
+    @property
+    def env_workload(self):
+        """(gap_id, work_id) of the tables in force."""
+        g, w = self._work_vec().env_workload
+        return int(g[0]), int(w[0])
+
+    def clear_workload_tables(self) -> None:
+        self._work_vec().clear_workload_tables()
 
     # ---- on-device snapshots (VecLoadBalanceEnv.snapshot / restore of the one env)
     def _snap_vec(self) -> "VecLoadBalanceEnv":

@@ -271,6 +271,21 @@ class VecMultiAgentLoadBalanceEnv:
     def trace_phase(self):
         return self.vec.trace_phase
 
+    def set_workload_tables(self, tables, gap_id, work_id) -> None:
+        """Per-env gap and flow-size tables: VecLoadBalanceEnv.set_workload_tables."""
+        self.vec.set_workload_tables(tables, gap_id, work_id)
+
+    def set_env_workload(self, gap_id=None, work_id=None) -> None:
+        """New per-env table ids (B,): VecLoadBalanceEnv.set_env_workload."""
+        self.vec.set_env_workload(gap_id, work_id)
+
+    def clear_workload_tables(self) -> None:
+        self.vec.clear_workload_tables()
+
+    @property
+    def env_workload(self):
+        return self.vec.env_workload
+
     def flow_stats(self, per_server: bool = False, hist: bool = False):
         """Exact flow statistics of an env made with flow_stats=True: VecLoadBalanceEnv.flow_stats."""
         return self.vec.flow_stats(per_server, hist)
