@@ -22,7 +22,8 @@
  *   - server failure / recovery (Bernoulli per step)  problem-03 THEORY.md §6.4 (:687-693)
  * plus the flow dynamics the reference does not have (Poisson arrivals, per-server
  * FIFO service, Philox4x32-10 counter RNG).  Those are "parity unpinned" against the reference:
- * this file is their executable specification.
+ * this file is their executable specification, itself held to DESIGN.md §3's text by an
+ * independent event simulator (tests/flowsim_ref.py, tests/test_flowsim_ref.py).
  *
  * Pinning: tests/test_oracle_golden.py checks the features, rewards and plumbing against golden
  * vectors produced by the reference Python itself (tests/golden/gen_golden.py), and Philox against
