@@ -625,6 +625,52 @@ int lbsim_flow_stats_quantiles(lbsim_t* h, const uint32_t* q_ppm, int nq, int pe
                                uint32_t* out_us, void* stream);
 int lbsim_flow_stats_clear(lbsim_t* h, const uint8_t* env_mask, void* stream);
 
+/* ---- scripted server availability (cluster sizes and outage schedules) ----
+ * The server side of a scenario, per env and on the device: which servers of env b are up at
+ * each phase of its episode.  A table is up[rows, P, S] bytes (DEVICE pointer), nonzero = up,
+ * rows = 1 (every env the same table) or B, 1 <= P <= 4096, each phase held for steps_per_phase
+ * (H >= 1) agent steps, cyclic (wrap != 0) or clamped at the last phase.  The phase rule is
+ * lbsim_set_rate_schedule's on k = ep_step[b].  P = 1 is a static per-env cluster.
+ * The table is applied at the START of every step launch, from the state as it is: one small
+ * kernel in front of the step compares, per (env, server), the wanted bit with the down section.
+ * up -> down is exactly the failure of fail_prob: the server's queued flows
+ * count as dropped, its queue and reservoirs are emptied (hc = head, last_tc = none, res_count =
+ * 0, lost_on = 0, a lost-FIN handle's duration count and pending guesses dropped,
+ * reservoir_mode VPP's bins zeroed), its cached features are zeroed, down = 1; its flow
+ * statistics are kept.  down -> up writes down = 0 and nothing else.  A down server shows as a
+ * zero row, is left out of the reward by the active rule, and takes no flows: SED / LSQ never
+ * pick it; under ALIAS an arrival sent to it is dropped, so the policy must give it weight 0.
+ * Resets are untouched: every server starts up, the warm-up and the reset observation have all
+ * S servers, and the first step of the episode applies phase 0.  On a next_step_reset handle an
+ * env with ep_step >= max_steps is skipped (that launch resets it) and served at its next step
+ * with k = 0.
+ * lbsim_server_avail_enable: before the handle's first lbsim_reset (LBSIM_EINVAL after it; a
+ * second call is a no-op).  Allocates the down section (zeroed) where the config did not, at the
+ * position a fail_prob > 0 handle has it, so the snapshot layout equals such a handle's, and
+ * plans the handle as one with failures (no one-wave kernel).  LBSIM_ENOTSUP on a handle with
+ * fail_prob > 0: a random recovery would bring a scripted-down server back.
+ * lbsim_set_server_avail: LBSIM_ENOTSUP without enable; LBSIM_EINVAL: P outside [1, 4096] or
+ * H < 1; LBSIM_ESHAPE: rows neither 1 nor B; LBSIM_ENOMEM: more than 2^31 - 1 entries
+ * (B * P * S), or a failed allocation.  The handle stores the table expanded to B rows (B * P * S
+ * bytes), allocated by the first call for a given P and rewritten in place, on `stream`, by later
+ * calls with the same P: a step captured into a hipGraph after the first call sees later tables
+ * on replay; a new P, H or wrap needs a new capture.  Any nonzero byte is up: nothing is
+ * validated on the device, and apart from the first allocation the call does not wait.
+ * lbsim_clear_server_avail: no table; the next step brings every server up (an allocated table
+ * takes all-up values, for the graphs that still read it).
+ * lbsim_get_server_avail: want_out[B, S] (u8: the set the next step launch will enforce; all 1
+ * for an env that launch resets), up_now_out[B, S] (u8: the current !down) and phase_out[B]
+ * (i32), DEVICE pointers, any may be NULL; the same kernel pointed at the outputs, on `stream`.
+ * lbsim_step / lbsim_reset gain no allocation and no synchronisation.  down is a state section,
+ * so snapshots, forks and lbsim_get_state carry it; the table is NOT in the snapshot: a restored
+ * or forked env is reconciled with its slot's table at its next step, by the rule above. */
+int lbsim_server_avail_enable(lbsim_t* h);
+int lbsim_set_server_avail(lbsim_t* h, const uint8_t* up, int32_t rows, int32_t phases,
+                           int32_t steps_per_phase, int32_t wrap, void* stream);
+int lbsim_clear_server_avail(lbsim_t* h);
+int lbsim_get_server_avail(lbsim_t* h, uint8_t* want_out, uint8_t* up_now_out, int32_t* phase_out,
+                           void* stream);
+
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/
  * alias_table.h:82-158, alias_table_build, rebuilt by lb_rl_node.c:92-111 from the weights the

@@ -189,6 +189,11 @@ _SIGNATURES = {
     "lbsim_flow_stats_get": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "lbsim_flow_stats_quantiles": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),
     "lbsim_flow_stats_clear": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_server_avail_enable": (ctypes.c_int, [_P]),
+    "lbsim_set_server_avail": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, _P]),
+    "lbsim_clear_server_avail": (ctypes.c_int, [_P]),
+    "lbsim_get_server_avail": (ctypes.c_int, [_P, _P, _P, _P, _P]),
     "lbsim_alias_tables": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P]),
     "lbsim_vose_tables": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P]),
     "lbsim_vose_sample": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, _P, ctypes.c_int64,

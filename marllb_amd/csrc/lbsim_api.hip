@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/lbsim.h"
+#include "lbsim_avail.h"
 #include "lbsim_internal.h"
 #include "lbsim_fused.h"
 #include "lbsim_nets.h"
@@ -102,6 +103,15 @@ struct lbsim {
   // lbsim_flow_stats_enable: one block (sum_us, hist, count, max_us), allocated once, never moved
   void* flow_buf = nullptr;
   FlowStats flow{};  // its arrays (null pointers: statistics off)
+  // lbsim_server_avail_enable: the handle has a down section whatever fail_prob says, and every
+  // step starts with avail_apply_kernel.  lbsim_set_server_avail: the table's block for
+  // avail_alloc_P phases ([B, P, S] bytes), moved only by a call with another P, and the table in
+  // force: avail_P phases (0: none, every server wanted up), each held for avail_H steps, cyclic
+  // or clamped.
+  bool avail_on = false;
+  uint8_t* avail_buf = nullptr;
+  int avail_alloc_P = 0;
+  int avail_P = 0, avail_H = 0, avail_wrap = 0;
   bool initialised;  // a full reset has been issued
   bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
@@ -300,7 +310,7 @@ std::vector<Section> sections(lbsim_t* h) {
     v.push_back({(void**)&s.norm_mean, BS * NF * 8});
     v.push_back({(void**)&s.norm_std, BS * NF * 8});
   }
-  if (h->cfg.fail_prob > 0.0f) v.push_back({(void**)&s.down, BS * 4});
+  if (h->cfg.fail_prob > 0.0f || s.down != nullptr) v.push_back({(void**)&s.down, BS * 4});
   if (h->prm.leak) v.push_back({(void**)&s.lost_on, BS * 4});
   // the duration plane: only when a flow's duration sample can differ from its fct; split
   // handles (lost-FIN): {us, ts} records, the duration count, the pending guesses, lf_over
@@ -827,6 +837,48 @@ int trace_select(lbsim_t* h, const uint8_t* mask, int mode, hipStream_t s) {
   return launch_check(h, "trace_gather_kernel");
 }
 
+// ---- scripted server availability (lbsim_set_server_avail; lbsim_avail.h)
+static_assert(kAvailK == K && kAvailHcHead == kHcHead && kAvailLastNone == kLastNone &&
+                  kAvailFeat + 1 == NF,
+              "lbsim_avail.h restates these for its host build");
+
+AvailState avail_state(const lbsim_t* h) {
+  const DevState& st = h->st;
+  const SimParams& p = h->prm;
+  AvailState a{};
+  a.ep_step = st.ep_step;
+  a.hc = st.hc;
+  a.last_tc = st.last_tc;
+  a.res_count = st.res_count;
+  a.res = reinterpret_cast<uint32_t*>(st.res);
+  a.fcache = st.fcache;
+  a.down = st.down;
+  a.lost_on = st.lost_on;
+  a.res_dur = st.res_dur;
+  a.res_count_dur = st.res_count_dur;
+  a.pend_hc = st.pend_hc;
+  a.B = h->B, a.S = h->S;
+  a.split = p.split, a.res_vpp = p.res_vpp;
+  a.max_steps = p.max_steps, a.next_reset = p.next_reset;
+  return a;
+}
+
+AvailTable avail_table(const lbsim_t* h) {
+  return AvailTable{h->avail_P > 0 ? h->avail_buf : nullptr, h->avail_P, h->avail_H,
+                    h->avail_wrap};
+}
+
+// In front of the first launch of a step of a handle with lbsim_server_avail_enable: each (env,
+// server) brought to what the table wants at the env's phase.  As sched_select: one small launch
+// on the step's stream, no allocation, no synchronisation, not in the launch log; any other
+// handle pays the one test.
+int avail_apply(lbsim_t* h, hipStream_t s) {
+  if (!h->avail_on) return LBSIM_OK;
+  hipLaunchKernelGGL(avail_apply_kernel, dim3(blocks256((size_t)h->B * h->S)), dim3(256), 0, s,
+                     avail_state(h), avail_table(h), AvailOut{}, 1, h->st.dropped);
+  return launch_check(h, "avail_apply_kernel");
+}
+
 // The bank's row offsets to the device (u32: fewer than 2^31 rows), for trace_gather_kernel.
 // Off the step path: it waits for the copy.
 int bank_begin_upload(lbsim_t* h) {
@@ -1047,7 +1099,7 @@ StepPlan plan_of(const lbsim_t* h) {
   const SimParams& p = h->prm;
   PlanInput in{};
   in.B = h->B, in.S = h->S, in.Q = p.Q, in.policy = p.policy;
-  in.trace = p.trace != 0, in.fail = p.fail_thr != 0u, in.leak = p.leak != 0;
+  in.trace = p.trace != 0, in.fail = p.fail_thr != 0u || h->avail_on, in.leak = p.leak != 0;
   in.split = p.split != 0, in.res_vpp = p.res_vpp != 0, in.dur_plane = dur_plane(p);
   in.next_reset = p.next_reset != 0;
   in.flow_stats = h->flow.hist != nullptr;
@@ -1231,6 +1283,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->rates_buf) (void)hipFree(h->rates_buf);
     if (h->sched_buf) (void)hipFree(h->sched_buf);
     if (h->flow_buf) (void)hipFree(h->flow_buf);
+    if (h->avail_buf) (void)hipFree(h->avail_buf);
     if (h->wtab_buf) (void)hipFree(h->wtab_buf);
     for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
   }
@@ -1328,6 +1381,8 @@ int lbsim_step_ex(lbsim_t* h, const void* action, int action_dtype,
   if (sched_select(h, nullptr, kModeStep, s) != LBSIM_OK)  // a rate schedule: each env's phase
     return LBSIM_EDEVICE;
   if (trace_select(h, nullptr, kModeStep, s) != LBSIM_OK)  // a trace schedule: each env's trace
+    return LBSIM_EDEVICE;
+  if (avail_apply(h, s) != LBSIM_OK)  // scripted availability: each env's servers at its phase
     return LBSIM_EDEVICE;
   if (h->plan.form == kStepWave) {
     ProfScope ps(h, s, 4);
@@ -1897,6 +1952,108 @@ int lbsim_flow_stats_enable(lbsim_t* h) {
   h->flow.max_us = h->flow.count + BS;
   h->plan = plan_of(h);  // a statistics handle is a full handle (make_plan)
   return LBSIM_OK;
+}
+
+int lbsim_server_avail_enable(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->avail_on) return LBSIM_OK;
+  if (h->prm.fail_thr != 0u)
+    return fail(h, LBSIM_ENOTSUP, "scripted availability on a handle with random failures "
+                                  "(fail_prob > 0): a random recovery would bring a scripted-down "
+                                  "server back");
+  if (h->reset_seen)
+    return fail(h, LBSIM_EINVAL, "lbsim_server_avail_enable must precede the handle's first "
+                                 "lbsim_reset (it adds a state section and changes which kernels "
+                                 "the handle launches)");
+  DeviceGuard g(h->device);
+  // the down section (fail_thr == 0 means fail_prob == 0: the config allocated none)
+  const size_t bytes = (size_t)h->B * h->S * 4;
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess)
+    return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", bytes);
+  if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(p);
+    return fail(h, LBSIM_EDEVICE, "server availability: hipMemset failed");
+  }
+  h->allocs.push_back(p);
+  h->st.down = (uint32_t*)p;
+  h->avail_on = true;
+  h->plan = plan_of(h);  // planned as a handle with failures: no one-wave kernel (make_plan)
+  return LBSIM_OK;
+}
+
+int lbsim_set_server_avail(lbsim_t* h, const uint8_t* up, int32_t rows, int32_t phases,
+                           int32_t steps_per_phase, int32_t wrap, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->avail_on)
+    return fail(h, LBSIM_ENOTSUP, "server availability is off: call lbsim_server_avail_enable "
+                                  "first");
+  if (up == nullptr) return fail(h, LBSIM_EINVAL, "server availability: up is NULL");
+  if (phases < 1 || phases > kAvailMaxPhases)
+    return fail(h, LBSIM_EINVAL, "server availability: phases must be in [1, %d] (got %d)",
+                kAvailMaxPhases, phases);
+  if (steps_per_phase < 1)
+    return fail(h, LBSIM_EINVAL, "server availability: steps_per_phase must be >= 1 (got %d)",
+                steps_per_phase);
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "server availability: rows must be 1 or num_envs = %d (got %d)",
+                h->B, rows);
+  const int P = phases;
+  const size_t per_env = (size_t)P * (size_t)h->S, n = (size_t)h->B * per_env;
+  if (n > (size_t)INT32_MAX)
+    return fail(h, LBSIM_ENOMEM, "server availability: num_envs * phases * num_servers = %zu "
+                                 "exceeds 2^31 - 1 table entries", n);
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  // the table: allocated by the first call for this P, rewritten in place by later ones
+  if (h->avail_buf == nullptr || h->avail_alloc_P != P) {
+    void* p = nullptr;
+    if (hipMalloc(&p, n) != hipSuccess) return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", n);
+    if (h->avail_buf != nullptr) (void)hipFree(h->avail_buf);  // (waits for the device)
+    h->avail_buf = (uint8_t*)p;
+    h->avail_alloc_P = P;
+    h->avail_P = 0;  // (until the table below is in place)
+  }
+  hipLaunchKernelGGL(avail_table_kernel, dim3(blocks256(n)), dim3(256), 0, s, up,
+                     rows == 1 ? (int64_t)0 : (int64_t)per_env, (int64_t)per_env, (int64_t)n,
+                     h->avail_buf);
+  const int rc = launch_check(h, "avail_table_kernel");
+  if (rc != LBSIM_OK) return rc;
+  h->avail_P = P;
+  h->avail_H = steps_per_phase;
+  h->avail_wrap = wrap != 0 ? 1 : 0;
+  return LBSIM_OK;
+}
+
+int lbsim_clear_server_avail(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->avail_on)
+    return fail(h, LBSIM_ENOTSUP, "server availability is off: call lbsim_server_avail_enable "
+                                  "first");
+  h->avail_P = h->avail_H = h->avail_wrap = 0;
+  if (h->avail_buf != nullptr) {
+    // a step captured into a graph while the table was set keeps reading it: every server up in
+    // every phase (no stream argument: the whole device is waited for)
+    DeviceGuard g(h->device);
+    const size_t n = (size_t)h->B * (size_t)h->avail_alloc_P * (size_t)h->S;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemset(h->avail_buf, 1, n) != hipSuccess)
+      return fail(h, LBSIM_EDEVICE, "server availability: clearing the table failed");
+  }
+  return LBSIM_OK;
+}
+
+int lbsim_get_server_avail(lbsim_t* h, uint8_t* want_out, uint8_t* up_now_out, int32_t* phase_out,
+                           void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->avail_on)
+    return fail(h, LBSIM_ENOTSUP, "server availability is off: call lbsim_server_avail_enable "
+                                  "first");
+  if (want_out == nullptr && up_now_out == nullptr && phase_out == nullptr) return LBSIM_OK;
+  DeviceGuard g(h->device);
+  hipLaunchKernelGGL(avail_apply_kernel, dim3(blocks256((size_t)h->B * h->S)), dim3(256), 0,
+                     (hipStream_t)stream, avail_state(h), avail_table(h),
+                     AvailOut{want_out, up_now_out, phase_out}, 0, (uint32_t*)nullptr);
+  return launch_check(h, "avail_apply_kernel");
 }
 
 int lbsim_flow_stats_get(lbsim_t* h, uint32_t* count, uint64_t* sum_us, uint32_t* max_us,

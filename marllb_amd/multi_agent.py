@@ -248,6 +248,21 @@ class VecMultiAgentLoadBalanceEnv:
     def rate_phase(self):
         return self.vec.rate_phase
 
+    def set_server_availability(self, up, steps_per_phase: int = 1, wrap: bool = True) -> None:
+        """Which servers are up, (P, S) shared or (B, P, S), over S = num_agents *
+        servers_per_agent servers in agent order: VecLoadBalanceEnv.set_server_availability (an
+        env made with server_availability=True)."""
+        self.vec.set_server_availability(up, steps_per_phase=steps_per_phase, wrap=wrap)
+
+    def set_cluster_sizes(self, n) -> None:
+        self.vec.set_cluster_sizes(n)
+
+    def clear_server_availability(self) -> None:
+        self.vec.clear_server_availability()
+
+    def servers_up(self):
+        return self.vec.servers_up()
+
     def set_trace_bank(self, bank) -> None:
         """A bank of traces: VecLoadBalanceEnv.set_trace_bank."""
         self.vec.set_trace_bank(bank)

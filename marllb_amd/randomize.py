@@ -169,3 +169,58 @@ def diurnal_trace_schedule(bank_rates, phases: int, num_envs: int, *, amplitude=
     target = rates.mean() * (1.0 + amp[:, None] * torch.sin(2.0 * math.pi * (j[None, :] + phi[:, None])))
     ids = (target[:, :, None] - rates[None, None, :]).abs().argmin(dim=2)
     return ids.to(device=device, dtype=torch.int32)
+
+
+# ---- server availability (VecLoadBalanceEnv.set_cluster_sizes / set_server_availability)
+
+def sample_cluster_sizes(num_envs: int, num_servers: int, min_servers: int = 1, seed: int = 0, *,
+                         device=None):
+    """-> (B,) int32 cluster sizes, uniform in [min_servers, num_servers]: cluster size as a
+    randomised domain inside one fixed-width batch (VecLoadBalanceEnv.set_cluster_sizes: env b
+    has its first n[b] servers up).  Deterministic for a seed."""
+    import torch
+
+    B, S, lo = int(num_envs), int(num_servers), int(min_servers)
+    if B < 1 or S < 1 or not 0 <= lo <= S:
+        raise ValueError(f"need num_envs >= 1 and 0 <= min_servers <= num_servers (got "
+                         f"{num_envs}, {min_servers}, {num_servers})")
+    g = torch.Generator().manual_seed(int(seed))
+    return torch.randint(lo, S + 1, (B,), generator=g, dtype=torch.int64).to(device=device,
+                                                                             dtype=torch.int32)
+
+
+def outage_schedule(num_envs: int, num_servers: int, phases: int, n_down: int, start: int,
+                    length: int, seed: int = 0, *, device=None):
+    """-> (B, phases, S) uint8 availability table (1 = up): per env one correlated outage, a
+    block of n_down consecutive servers (wrapping past the last one) whose first server is
+    uniform over the S servers, down over the phases [start, start + length) and up otherwise
+    (VecLoadBalanceEnv.set_server_availability).  Deterministic for a seed."""
+    import torch
+
+    B, S, P = int(num_envs), int(num_servers), int(phases)
+    n, lo, ln = int(n_down), int(start), int(length)
+    if B < 1 or S < 1 or P < 1 or not 0 <= n <= S or lo < 0 or ln < 0:
+        raise ValueError(f"need num_envs, num_servers, phases >= 1, 0 <= n_down <= num_servers, "
+                         f"start >= 0 and length >= 0 (got {num_envs}, {num_servers}, {phases}, "
+                         f"{n_down}, {start}, {length})")
+    g = torch.Generator().manual_seed(int(seed))
+    first = torch.randint(0, S, (B,), generator=g, dtype=torch.int64)
+    hit = ((torch.arange(S)[None, :] - first[:, None]) % S) < n          # (B, S)
+    j = torch.arange(P)
+    during = (j >= lo) & (j < lo + ln)                                   # (P,)
+    up = ~(hit[:, None, :] & during[None, :, None])
+    return up.to(device=device, dtype=torch.uint8)
+
+
+def rolling_restart_schedule(num_servers: int, phases: int, *, device=None):
+    """-> (phases, S) uint8 availability table (1 = up), shared by every env: a rolling restart,
+    server j % S down in phase j for j = 1 .. phases - 1; phase 0 (the phase of an episode's
+    first steps) has every server up."""
+    import torch
+
+    S, P = int(num_servers), int(phases)
+    if S < 1 or P < 1:
+        raise ValueError(f"need num_servers >= 1 and phases >= 1 (got {num_servers}, {phases})")
+    j = torch.arange(P)
+    down = (torch.arange(S)[None, :] == (j % S)[:, None]) & (j > 0)[:, None]
+    return (~down).to(device=device, dtype=torch.uint8)
