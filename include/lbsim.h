@@ -671,6 +671,38 @@ int lbsim_clear_server_avail(lbsim_t* h);
 int lbsim_get_server_avail(lbsim_t* h, uint8_t* want_out, uint8_t* up_now_out, int32_t* phase_out,
                            void* stream);
 
+/* ---- hidden cross traffic (flows the agent's balancer did not forward) ----
+ * On an enabled handle each arrival is, with probability share[b], a flow of another balancer:
+ * it goes to a server drawn from the hidden weights of its env (the action is ignored), occupies
+ * the FIFO and is served like any flow, and is seen nowhere: not in observation column 0, the
+ * SED / LSQ scores, assign counts, the reservoirs, the reward or the flow statistics.  A hidden
+ * flow that meets a full or down server is dropped and counted in `dropped`.  The decision is a
+ * hash of (seed, global env id, episode, arrival index): independent of kernel form and sharding.
+ * The visible arrival rate is (1 - share) * arrival_rate.
+ * lbsim_cross_traffic_enable: before the handle's first lbsim_reset (LBSIM_EINVAL after it; a
+ * second call is a no-op).  LBSIM_ENOTSUP on a handle with lost_fin_prob > 0.  Allocates the
+ * lost_on section (zeroed) at the position an n_flow_on_mode VPP lost-FIN handle has it -- on
+ * such a handle lost_on[b, s] is, as an int32, minus the hidden flows queued at the server -- and
+ * makes the handle a full one (dynamics_group_full_kernel, two launches).  Every share starts 0:
+ * results equal a handle without cross traffic.
+ * lbsim_set_cross_traffic: share[rows] f32 in [0, 1] and weight[rows, S] f32 (finite, >= 0, each
+ * row's sum > 0; NULL = uniform), DEVICE pointers, rows = 1 (every env the same) or B
+ * (LBSIM_ESHAPE otherwise).  Stored as thr[b] = rint(share * 2^24) and the 24-bit edges
+ * cum[b, s] = floor(2^24 c_s / c_{S-1}), c the sequential f64 prefix sum of the weights,
+ * cum[b, S-1] = 2^24.  Converted into a staging copy on `stream`, and the call waits for it: with
+ * any value out of range (NaN included) it returns LBSIM_EINVAL and what was in force stays.  The
+ * arrays are allocated by the first call and rewritten in place: a step captured into a hipGraph
+ * sees later values.  New values apply to arrivals assigned from the next launch on (a reset's
+ * warm-up included); queued flows keep their flag.  Not part of the snapshot.
+ * lbsim_get_cross_traffic: thr_out[B] and cum_out[B, S] (u32, DEVICE pointers, either may be
+ * NULL), asynchronous on `stream`.  lbsim_clear_cross_traffic: every share 0, in place.
+ * set / get / clear return LBSIM_ENOTSUP on a handle that was not enabled. */
+int lbsim_cross_traffic_enable(lbsim_t* h);
+int lbsim_set_cross_traffic(lbsim_t* h, const float* share, const float* weight, int32_t rows,
+                            void* stream);
+int lbsim_get_cross_traffic(lbsim_t* h, uint32_t* thr_out, uint32_t* cum_out, void* stream);
+int lbsim_clear_cross_traffic(lbsim_t* h, void* stream);
+
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/
  * alias_table.h:82-158, alias_table_build, rebuilt by lb_rl_node.c:92-111 from the weights the

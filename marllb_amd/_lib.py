@@ -189,6 +189,10 @@ _SIGNATURES = {
     "lbsim_flow_stats_get": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "lbsim_flow_stats_quantiles": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),
     "lbsim_flow_stats_clear": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_cross_traffic_enable": (ctypes.c_int, [_P]),
+    "lbsim_set_cross_traffic": (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, _P]),
+    "lbsim_get_cross_traffic": (ctypes.c_int, [_P, _P, _P, _P]),
+    "lbsim_clear_cross_traffic": (ctypes.c_int, [_P, _P]),
     "lbsim_server_avail_enable": (ctypes.c_int, [_P]),
     "lbsim_set_server_avail": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_int32, _P]),

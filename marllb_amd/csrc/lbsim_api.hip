@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#define LBSIM_CROSS_KERNELS  // cross_convert_kernel is defined in this object (lbsim_cross.h)
 #include "../../include/lbsim.h"
 #include "lbsim_avail.h"
 #include "lbsim_internal.h"
@@ -112,6 +113,11 @@ struct lbsim {
   uint8_t* avail_buf = nullptr;
   int avail_alloc_P = 0;
   int avail_P = 0, avail_H = 0, avail_wrap = 0;
+  // lbsim_cross_traffic_enable: one block of u32, allocated once and never moved -- the live
+  // thr[B] and cum[B*S] the full dynamics kernel reads (CrossTraffic), their staging copies (a call
+  // converts into these and only a valid one is copied over the live arrays), the offender count
+  void* cross_buf = nullptr;
+  CrossTraffic cross{};  // the live arrays (null pointers: the handle has no cross traffic)
   bool initialised;  // a full reset has been issued
   bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
@@ -311,7 +317,8 @@ std::vector<Section> sections(lbsim_t* h) {
     v.push_back({(void**)&s.norm_std, BS * NF * 8});
   }
   if (h->cfg.fail_prob > 0.0f || s.down != nullptr) v.push_back({(void**)&s.down, BS * 4});
-  if (h->prm.leak) v.push_back({(void**)&s.lost_on, BS * 4});
+  // (a cross-traffic handle keeps minus its hidden flows there: lbsim_cross_traffic_enable)
+  if (h->prm.leak || h->cross_buf != nullptr) v.push_back({(void**)&s.lost_on, BS * 4});
   // the duration plane: only when a flow's duration sample can differ from its fct; split
   // handles (lost-FIN): {us, ts} records, the duration count, the pending guesses, lf_over
   if (dur_plane(h->prm)) v.push_back({(void**)&s.res_dur, BSK * (h->prm.split ? 8 : 4)});
@@ -1091,7 +1098,7 @@ std::string short_kernel_name(const char* raw) {
   return s;
 }
 
-LaunchCtx ctx(const lbsim_t* h) { return LaunchCtx{h->plan, h->st, h->prm, h->flow}; }
+LaunchCtx ctx(const lbsim_t* h) { return LaunchCtx{h->plan, h->st, h->prm, h->flow, h->cross}; }
 
 // The handle's plan: the process's overrides are read on the first call and kept.
 StepPlan plan_of(const lbsim_t* h) {
@@ -1104,6 +1111,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.next_reset = p.next_reset != 0;
   in.flow_stats = h->flow.hist != nullptr;
   in.work_tables = h->wtab_T > 0;
+  in.cross_traffic = h->cross_buf != nullptr;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -1283,6 +1291,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->rates_buf) (void)hipFree(h->rates_buf);
     if (h->sched_buf) (void)hipFree(h->sched_buf);
     if (h->flow_buf) (void)hipFree(h->flow_buf);
+    if (h->cross_buf) (void)hipFree(h->cross_buf);
     if (h->avail_buf) (void)hipFree(h->avail_buf);
     if (h->wtab_buf) (void)hipFree(h->wtab_buf);
     for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
@@ -1951,6 +1960,111 @@ int lbsim_flow_stats_enable(lbsim_t* h) {
   h->flow.count = h->flow.hist + BS * kFlowBins;
   h->flow.max_us = h->flow.count + BS;
   h->plan = plan_of(h);  // a statistics handle is a full handle (make_plan)
+  return LBSIM_OK;
+}
+
+// ---- hidden cross traffic (the rule and the conversion kernel: lbsim_cross.h)
+
+int lbsim_cross_traffic_enable(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->cross_buf != nullptr) return LBSIM_OK;
+  if (h->prm.lf_thr != 0u)
+    return fail(h, LBSIM_ENOTSUP, "cross traffic on a lost-FIN handle (lost_fin_prob > 0): the "
+                                  "split reservoirs and n_flow_on_mode VPP use the lost_on "
+                                  "counter with the opposite sign");
+  if (h->reset_seen)
+    return fail(h, LBSIM_EINVAL, "lbsim_cross_traffic_enable must precede the handle's first "
+                                 "lbsim_reset (it adds a state section and changes which kernels "
+                                 "the handle launches)");
+  DeviceGuard g(h->device);
+  const size_t B = (size_t)h->B, BS = B * h->S;
+  const size_t words = 2 * (B + BS) + 1, lost_bytes = BS * 4;
+  void *p = nullptr, *lost = nullptr;
+  if (hipMalloc(&p, words * 4) != hipSuccess)
+    return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", words * 4);
+  if (hipMalloc(&lost, lost_bytes) != hipSuccess) {
+    (void)hipFree(p);
+    return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", lost_bytes);
+  }
+  // share 0 and uniform edges in the live arrays
+  uint32_t* const w = (uint32_t*)p;
+  bool ok = hipMemset(p, 0, words * 4) == hipSuccess && hipMemset(lost, 0, lost_bytes) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(cross_convert_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0,
+                       nullptr, (const float*)nullptr, (int64_t)0, (const float*)nullptr,
+                       (int64_t)0, h->B, h->S, w, w + B, w + 2 * (B + BS));
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipFree(p);
+    (void)hipFree(lost);
+    return fail(h, LBSIM_EDEVICE, "cross traffic: device init failed");
+  }
+  h->cross_buf = p;
+  h->cross.thr = w;
+  h->cross.cum = w + B;
+  h->allocs.push_back(lost);
+  h->st.lost_on = (uint32_t*)lost;
+  h->plan = plan_of(h);  // a cross-traffic handle is a full handle (make_plan)
+  return LBSIM_OK;
+}
+
+int lbsim_set_cross_traffic(lbsim_t* h, const float* share, const float* weight, int32_t rows,
+                            void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->cross_buf == nullptr)
+    return fail(h, LBSIM_ENOTSUP, "cross traffic is off: call lbsim_cross_traffic_enable first");
+  if (share == nullptr) return fail(h, LBSIM_EINVAL, "cross traffic: share is NULL");
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "cross traffic: rows must be 1 or num_envs = %d (got %d)", h->B,
+                rows);
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t B = (size_t)h->B, BS = B * h->S;
+  uint32_t* const live = (uint32_t*)h->cross_buf;
+  uint32_t* const stg = live + (B + BS);
+  uint32_t* const bad = live + 2 * (B + BS);
+  if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "cross traffic: hipMemsetAsync failed");
+  const int64_t rs = rows == 1 ? 0 : 1;
+  hipLaunchKernelGGL(cross_convert_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s,
+                     share, rs, weight, rs * (int64_t)h->S, h->B, h->S, stg, stg + B, bad);
+  const int rc = launch_check(h, "cross_convert_kernel");
+  if (rc != LBSIM_OK) return rc;
+  uint32_t nbad = 0;
+  if (hipMemcpyAsync(&nbad, bad, sizeof(nbad), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "cross traffic: conversion failed");
+  if (nbad != 0u)  // the live arrays are untouched: the previous values stay in force
+    return fail(h, LBSIM_EINVAL, "cross traffic: %u row(s) out of range (share must be in [0, 1]; "
+                                 "weights finite and >= 0 with a positive sum; NaN rejected)", nbad);
+  if (hipMemcpyAsync(live, stg, (B + BS) * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "cross traffic: device copy failed");
+  return LBSIM_OK;
+}
+
+int lbsim_get_cross_traffic(lbsim_t* h, uint32_t* thr_out, uint32_t* cum_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->cross_buf == nullptr)
+    return fail(h, LBSIM_ENOTSUP, "cross traffic is off: call lbsim_cross_traffic_enable first");
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t B = (size_t)h->B, BS = B * h->S;
+  bool ok = true;
+  if (thr_out != nullptr)
+    ok &= hipMemcpyAsync(thr_out, h->cross.thr, B * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  if (cum_out != nullptr)
+    ok &= hipMemcpyAsync(cum_out, h->cross.cum, BS * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
+  return ok ? LBSIM_OK : fail(h, LBSIM_EDEVICE, "cross traffic: device copy failed");
+}
+
+int lbsim_clear_cross_traffic(lbsim_t* h, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->cross_buf == nullptr)
+    return fail(h, LBSIM_ENOTSUP, "cross traffic is off: call lbsim_cross_traffic_enable first");
+  DeviceGuard g(h->device);
+  if (hipMemsetAsync(h->cross.thr, 0, (size_t)h->B * 4, (hipStream_t)stream) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "cross traffic: hipMemsetAsync failed");
   return LBSIM_OK;
 }
 

@@ -26,6 +26,7 @@
 // [slot][lane].
 #pragma once
 
+#include "lbsim_cross.h"
 #include "lbsim_kernels.h"
 
 namespace lbk {
@@ -150,6 +151,14 @@ __device__ __forceinline__ void flow_stats_add(SrvLane& V, uint32_t fct) {
   V.fs_max = fct > V.fs_max ? fct : V.fs_max;
   V.fs_row[flow_bin(fct)] += 1u;
 }
+
+// Hidden cross traffic (lbsim_cross.h) as a lane of a full handle sees it: the
+// env's threshold, the lane's own cumulative edge (read once, in the wave's prologue), and the
+// episode's salt.  on: the handle has the arrays (wave-uniform: the kernel's argument).
+struct CrossLane {
+  bool on = false;
+  uint32_t thr = 0u, edge = 0u, salt = 0u;
+};
 
 // ALIAS table of the group in LDS: word f of active position k at [f][gbase + k].  Every lane of
 // the group builds the same table (same values to the same words).
@@ -296,7 +305,8 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
                                                  int32_t* atab, int4* acache, uint2* const my_res,
                                                  int2* const my_ring, bool fs_on = false,
                                                  const TraceSel& ts = TraceSel{},
-                                                 const WorkSel& ws = WorkSel{}) {
+                                                 const WorkSel& ws = WorkSel{},
+                                                 const CrossLane& cx = CrossLane{}) {
   constexpr int WL = kGroupWL;
   constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
   constexpr bool alias = POLICY == kPolicyAlias;
@@ -361,10 +371,14 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
     const bool arrival_due = E.next_arr < dt;  // the same in every lane of the group
     const int32_t th = arrival_due ? E.next_arr : dt;
     const bool due = V.act && V.cnt > 0 && V.head_tc <= th;
-    if constexpr (FULL) {  // n_flow_on_mode VPP: a popped lost-FIN flow stays in n_flow_on
-      if (p.leak && due &&
-          lf_lost(p, gc.base_ms * 1000u + gc.base_rem + (uint32_t)wslot(V.lh)->y, E.gid, E.episode))
+    if constexpr (FULL) {
+      if (cx.on) {  // cross traffic: a popped hidden flow (its flag) leaves the hidden count
+        if (due && wslot(V.lh)->y == kHiddenTa) V.lost += 1;
+      } else if (p.leak && due &&  // n_flow_on_mode VPP: a popped lost-FIN flow stays in n_flow_on
+                 lf_lost(p, gc.base_ms * 1000u + gc.base_rem + (uint32_t)wslot(V.lh)->y, E.gid,
+                         E.episode)) {
         V.lost += 1;
+      }
     }
     if (due && V.cnt > WL) {  // rare: the slot the pop frees takes queue entry WL from the ring
       int pw = V.head + WL;
@@ -391,7 +405,8 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
     const int32_t ta = E.next_arr;
     if constexpr (!alias) {
       // the data plane's n_flow_on: the queue, plus the lost-FIN flows it never decremented
-      // (n_flow_on_mode VPP only: the general loop; V.lost = 0 otherwise)
+      // (n_flow_on_mode VPP only: the general loop; V.lost = 0 otherwise); on a cross-traffic
+      // handle V.lost is minus the hidden flows queued: the visible count
       const int32_t nfo = FULL ? V.cnt + V.lost : V.cnt;
       if constexpr (lsq) {
         V.score = (float)nfo;
@@ -441,6 +456,20 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
       const uint64_t nan = FAST ? 0ull : group_bits<G>(__ballot(V.score != V.score), gbase);
       chosen = c0 < 0 ? -1 : ((((tie | nan) >> c0) & 1u) ? c0 : (tie ? __builtin_ctzll(tie) : -1));
     }
+    // ---- cross traffic: arrival arr_idx may be one the balancer did not forward (a hash of the
+    //      arrival index, not of its Philox words); its server comes from the hidden weights' edges
+    //      (one ballot: the edges at or below the word), whatever the action says
+    bool hid = false;
+    if constexpr (FULL) {
+      if (cx.on) {
+        const uint32_t h = cross_hash(E.arr_idx, cx.salt);
+        hid = cross_hidden(h, cx.thr);
+        const uint32_t x = cross_pick_word(h);
+        const int pick =
+            __builtin_popcountll(group_bits<G>(__ballot(V.act && cx.edge <= x), gbase));
+        chosen = hid ? (((em >> pick) & 1u) ? pick : -1) : chosen;
+      }
+    }
     const bool push = arr && chosen >= 0;
     E.dropped += (arr && chosen < 0) ? 1u : 0u;
     const bool mine = push && s == chosen;
@@ -453,11 +482,12 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
     const bool ins = mine && tc_a <= dt;  // completes in this step: its sample now
 
     // ---- the pushed flow's Algorithm R draw is this arrival's word r (E.u3)
-    const int slot = (FULL && p.res_vpp) ? (int)(E.u3 >> 25) : reservoir_slot_r32(V.rcnt, E.u3);
+    int slot = (FULL && p.res_vpp) ? (int)(E.u3 >> 25) : reservoir_slot_r32(V.rcnt, E.u3);
     bool split = false;  // split handles (lost-FIN): their own inserts (split_complete)
     if constexpr (FULL) {
       // flow statistics: the true tc - ta, before a lost-FIN flow turns into its guess
-      if (fs_on && ins) flow_stats_add(V, (uint32_t)(tc_a - ta));
+      if (hid) slot = -1;  // (a hidden flow leaves no record)
+      if (fs_on && ins && !hid) flow_stats_add(V, (uint32_t)(tc_a - ta));
       split = p.split != 0;
       if (split && ins) {
         const uint64_t base_us = (uint64_t)gc.base_ms * 1000u + gc.base_rem;
@@ -480,7 +510,7 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
     // (a branch-free push, non-pushing lanes storing to scratch slots, measured 3 us slower at
     // 65536 x 4, profiles/r06e/)
     if (mine) {
-      const int2 e = make_int2(tc_a, ta);
+      const int2 e = make_int2(tc_a, FULL ? (hid ? kHiddenTa : ta) : ta);  // (hidden: the flag)
       if (V.cnt < WL) {
         *wslot((V.lh + V.cnt) & (WL - 1)) = e;
       } else {
@@ -490,10 +520,16 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
         asm volatile("");  // no flat store (see dynamics_kernel)
       }
       V.tail = tc_a;
-      V.assigned += 1;
+      if constexpr (FULL) {  // (a hidden flow: no assignment, one more in the hidden count)
+        V.assigned += hid ? 0 : 1;
+        V.lost -= hid ? 1 : 0;
+      } else {
+        V.assigned += 1;
+      }
       V.head_tc = V.cnt == 0 ? tc_a : V.head_tc;
       V.cnt += 1;
-      V.rcnt = (ins && !split) ? count_inc(V.rcnt) : V.rcnt;
+      if constexpr (FULL) V.rcnt = (ins && !split && !hid) ? count_inc(V.rcnt) : V.rcnt;
+      else V.rcnt = (ins && !split) ? count_inc(V.rcnt) : V.rcnt;
     }
 
     // ---- next arrival (identical in every lane of the group): arrival arr_idx + 1 from the
@@ -515,7 +551,8 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                                                int gbase, float w_own, const float (&wall)[G],
                                                int2* win, int32_t* atab, int4* acache,
                                                bool fs_on = false,
-                                               const TraceSel& ts = TraceSel{}) {
+                                               const TraceSel& ts = TraceSel{},
+                                               const CrossLane& cx = CrossLane{}) {
   constexpr int WL = kGroupWL;
   const int S = p.S, Q = p.Q;
   const int32_t dt = p.dt_us;
@@ -578,7 +615,12 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
     int32_t prev = V.last;
     uint32_t rc = V.rcnt;
     auto insert = [&](int32_t etc, int32_t eta) {
-      if constexpr (FULL) {  // flow statistics: the true tc - ta, lost-FIN or not
+      if constexpr (FULL) {
+        if (eta == kHiddenTa) {  // cross traffic: a hidden flow is no sample, only the predecessor
+          prev = etc;            // of the next one (duration_mode SERVICE)
+          return;
+        }
+        // flow statistics: the true tc - ta, lost-FIN or not
         if (fs_on) flow_stats_add(V, (uint32_t)(etc - eta));
       }
       if (FULL && p.split) {  // lost-FIN: split reservoirs and deferred guesses (split_complete)
@@ -641,7 +683,7 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
     group_event_loop<G, POLICY, TRACE, false, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                                    acache, my_res, my_ring, fs_on, ts, ws);
+                                                    acache, my_res, my_ring, fs_on, ts, ws, cx);
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
   } else if (__all(finite)) {
@@ -655,17 +697,20 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
   // ---- rebase to the next step's start (this lane's server)
   E.next_arr -= dt;
   if (V.act) {
+    // (FULL: a hidden flow's arrival word is its flag, kHiddenTa, and stays)
     for (int i = 0; i < WL && i < V.cnt; ++i) {
       int2* e = wslot((V.lh + i) & (WL - 1));
       e->x -= dt;
-      e->y -= dt;
+      if constexpr (FULL) e->y = e->y == kHiddenTa ? kHiddenTa : e->y - dt;
+      else e->y -= dt;
     }
     int pos = V.head + WL;
     if (pos >= Q) pos -= Q;
     for (int i = WL; i < V.cnt; ++i) {
       int2 e = my_ring[(uint32_t)pos];
       e.x -= dt;
-      e.y -= dt;
+      if constexpr (FULL) e.y = e.y == kHiddenTa ? kHiddenTa : e.y - dt;
+      else e.y -= dt;
       my_ring[(uint32_t)pos] = e;
       pos = (pos + 1 == Q) ? 0 : pos + 1;
     }
@@ -694,7 +739,8 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
                                                const void* action, int action_dtype,
                                                int32_t* assign_out, const uint8_t* reset_mask,
                                                uint32_t wave, int lane, DynGroupLds<POLICY>& L,
-                                               const FlowStats& fs = FlowStats{}) {
+                                               const FlowStats& fs = FlowStats{},
+                                               const CrossTraffic& ct = CrossTraffic{}) {
   static_assert(G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64,
                 "group = a power of two lanes of the wave");
   constexpr int WL = kGroupWL;
@@ -746,6 +792,14 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
   float wall[G];
   float w_own = 1.0f;
   const bool fs_on = FULL && fs.hist != nullptr;  // wave-uniform: the kernel's argument
+  CrossLane cx;  // cross traffic: the env's threshold and this lane's edge, read once
+  if constexpr (FULL) {
+    if (ct.thr != nullptr) {  // wave-uniform
+      cx.on = true;
+      cx.thr = ct.thr[b];
+      cx.edge = V.act ? ct.cum[sb] : kCrossOne;
+    }
+  }
 
   auto reset_in = [&]() {  // a new episode (env.py:186-213): its first arrival, empty servers
     E.episode = st.episode[b] + 1u;
@@ -808,6 +862,12 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     if (FULL && p.split) lfo_base = st.lf_over[b];
     if (FULL && V.act) {
       if (p.leak) V.lost = (int32_t)st.lost_on[sb];
+      // cross traffic: minus the hidden flows queued.  Its own if constexpr, not `p.leak ||
+      // cx.on` above: a discarded statement keeps cx out of this lambda's captures in the plain
+      // kernels, whose register allocation moved with the one more reference
+      if constexpr (FULL) {
+        if (cx.on) V.lost = (int32_t)st.lost_on[sb];
+      }
       if (p.split) {
         V.rcnt_d = st.res_count_dur[sb];
         const uint32_t ph = st.pend_hc[sb];
@@ -871,15 +931,22 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
       st.ep_return[b] = 0.0;
     }
   };
+  auto cross_in = [&]() {  // cross traffic: the salt of the episode that load_in / reset_in gave
+    if constexpr (FULL) {
+      if (cx.on) cx.salt = cross_salt(p.key0, p.key1, E.gid, E.episode);
+    }
+  };
   if constexpr (MODE == kModeStep) {
     load_in();
+    cross_in();
     sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w_own, wall, win, atab,
-                                           acache, fs_on, ts);
+                                           acache, fs_on, ts, cx);
   } else if constexpr (MODE == kModeReset) {
     reset_in();
+    cross_in();
     for (int k = 0; k < p.warmup_steps; ++k)
       sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, 1.0f, wall, win, atab,
-                                             acache, fs_on, ts);
+                                             acache, fs_on, ts, cx);
     reset_out(0);
   } else {
     // kModeStepNR (next-step auto-reset): an env whose last step returned done resets in place of
@@ -891,11 +958,12 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     const bool rs = st.ep_step[b] >= p.max_steps;
     if (rs) reset_in();
     else load_in();
+    cross_in();
     const int nsteps = rs ? p.warmup_steps : 1;
     const float w = rs ? 1.0f : w_own;
     for (int k = 0; k < nsteps; ++k)
       sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w, wall, win, atab,
-                                             acache, fs_on, ts);
+                                             acache, fs_on, ts, cx);
     if (rs) reset_out(-1);
   }
 
@@ -922,7 +990,7 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     st.last_tc[sb] = V.last;
     st.res_count[sb] = V.rcnt;
     if (st.down != nullptr) st.down[sb] = V.qcap == 0 ? 1u : 0u;
-    if (FULL && p.leak) st.lost_on[sb] = (uint32_t)V.lost;
+    if (FULL && (p.leak || cx.on)) st.lost_on[sb] = (uint32_t)V.lost;
     if (FULL && V.fs_row != nullptr) {
       fs.count[sb] = V.fs_cnt;
       fs.max_us[sb] = V.fs_max;
@@ -962,14 +1030,16 @@ __global__ void __launch_bounds__(64, WAVES)
 
 // The same for a full handle (group_event_loop's FULL: n_flow_on_mode VPP, a duration plane,
 // lost-FIN deferral, reservoir_mode VPP, flow statistics): the general event loop with every
-// feature, on its own register budget.  fs: the flow statistics' arrays (null pointers: off).
+// feature, on its own register budget.  fs: the flow statistics' arrays (null pointers: off); ct:
+// the cross traffic's (lbsim_cross.h; null pointers: the handle has none).
 template <int G, int MODE, int POLICY, bool TRACE>
 __global__ void __launch_bounds__(64)
     dynamics_group_full_kernel(DevState st, SimParams p, const void* action, int action_dtype,
-                               int32_t* assign_out, const uint8_t* reset_mask, FlowStats fs) {
+                               int32_t* assign_out, const uint8_t* reset_mask, FlowStats fs,
+                               CrossTraffic ct) {
   __shared__ DynGroupLds<POLICY> L;
   dyn_group_wave<G, MODE, POLICY, TRACE, true>(st, p, action, action_dtype, assign_out,
-                                               reset_mask, blockIdx.x, (int)threadIdx.x, L, fs);
+                                               reset_mask, blockIdx.x, (int)threadIdx.x, L, fs, ct);
 }
 
 }  // namespace lbk

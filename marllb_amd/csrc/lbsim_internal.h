@@ -1,6 +1,7 @@
 // lbsim_internal.h — host-side glue between the extern "C" API (lbsim_api.hip) and the translation
 // units that instantiate the templated kernels (compiled in parallel, linked into liblbsim.so):
 //
+//   lbsim_cross.h      hidden cross traffic: the host / device rule and its conversion kernel
 //   lbsim_plan.h       make_plan: which kernels a handle's step and reset launch, decided once
 //                      (host-only; the launchers below turn the plan into template arguments)
 //   lbsim_dyn.hip      dynamics_kernel / dynamics_group_kernel launchers; built three times
@@ -18,6 +19,7 @@
 #include <type_traits>
 
 #include "../../include/lbsim.h"
+#include "lbsim_cross.h"
 #include "lbsim_kernels.h"
 #include "lbsim_plan.h"
 
@@ -48,6 +50,7 @@ struct LaunchCtx {
   const DevState& st;
   const SimParams& prm;
   const FlowStats& flow;  // the full group dynamics' flow statistics (null pointers: off)
+  const CrossTraffic& cross;  // and its cross traffic (lbsim_cross.h; null pointers: none)
 };
 
 // Runtime value -> template argument: pick<2, 4, 8>(v, f) calls f(std::integral_constant<int, v>)

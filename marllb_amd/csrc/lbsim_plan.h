@@ -42,8 +42,9 @@ struct Overrides {
   }
 };
 
-// What the plan depends on: fixed when the handle is created, but for flow_stats (set before the
-// first reset) and work_tables (the plan is made again when tables come into force or are cleared).
+// What the plan depends on: fixed when the handle is created, but for flow_stats and
+// cross_traffic (set before the first reset) and work_tables (the plan is made again when tables
+// come into force or are cleared).
 struct PlanInput {
   int B, S, Q;
   int policy;       // lbsim_assign_policy
@@ -59,6 +60,7 @@ struct PlanInput {
   int simds;        // SIMDs of the device (CUs x 4)
   bool flow_stats;  // exact flow statistics are on (lbsim_flow_stats_enable)
   bool work_tables;  // workload tables are in force (lbsim_set_workload_tables)
+  bool cross_traffic = false;  // hidden cross traffic is on (lbsim_cross_traffic_enable)
 };
 
 enum StepForm { kStepWave, kStepGroupFused, kStepTwoLaunch };
@@ -116,7 +118,8 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
   // a statistics handle plans exactly as a reservoir_mode VPP one does.
   // Workload tables: their lookups are compiled into the full form alone (the runtime test in the
   // shared instantiations moved the headline kernel's registers).
-  const bool full_only = in.res_vpp || in.flow_stats || in.work_tables;
+  // Cross traffic: the hidden flows' decision, flag and count are compiled into the full form alone.
+  const bool full_only = in.res_vpp || in.flow_stats || in.work_tables || in.cross_traffic;
   const bool wave_fits = ov.dyn_wave != 0 && !ov.group_lanes_set &&
                          in.dyn_mapping != LBSIM_DYN_ENV_PER_LANE && S <= 8 && in.Q <= 32 &&
                          in.policy != LBSIM_POLICY_ALIAS && !in.fail && !in.leak && !in.split &&

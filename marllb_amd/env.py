@@ -457,6 +457,37 @@ class Handle:
                                              ctypes.c_void_p(self._stream())))
         return out
 
+    def enable_cross_traffic(self) -> None:
+        """Hidden cross traffic from now on (lbsim_cross_traffic_enable): before the handle's
+        first reset (ValueError after it); LbsimError ENOTSUP with lost_fin_prob > 0."""
+        self.check(self.lib.lbsim_cross_traffic_enable(self.h))
+
+    def set_cross_traffic(self, share, weight=None, *, rows: int) -> None:
+        """Shares and hidden weights (lbsim_set_cross_traffic): share (rows,) and weight
+        (rows, S) or None (uniform), f32 contiguous tensors on the handle's device, rows = 1 or
+        B."""
+        self.check(self.lib.lbsim_set_cross_traffic(
+            self.h, ctypes.c_void_p(share.data_ptr()),
+            ctypes.c_void_p(weight.data_ptr() if weight is not None else None), int(rows),
+            ctypes.c_void_p(self._stream())))
+
+    def cross_traffic(self):
+        """(thr (B,), cum (B, S)) int32 device tensors: the 24-bit thresholds and cumulative
+        edges in force (lbsim_get_cross_traffic)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        B, S = int(self.cfg.num_envs), int(self.cfg.num_servers)
+        thr = torch.empty(B, dtype=torch.int32, device=dev)
+        cum = torch.empty((B, S), dtype=torch.int32, device=dev)
+        self.check(self.lib.lbsim_get_cross_traffic(self.h, ctypes.c_void_p(thr.data_ptr()),
+                                                    ctypes.c_void_p(cum.data_ptr()),
+                                                    ctypes.c_void_p(self._stream())))
+        return thr, cum
+
+    def clear_cross_traffic(self) -> None:
+        """Every share 0 (lbsim_clear_cross_traffic), on the current stream."""
+        self.check(self.lib.lbsim_clear_cross_traffic(self.h, ctypes.c_void_p(self._stream())))
+
     def enable_server_avail(self) -> None:
         """Scripted server availability from now on (lbsim_server_avail_enable): before the
         handle's first reset (ValueError after it); LbsimError ENOTSUP with fail_prob > 0."""
@@ -545,13 +576,18 @@ class VecLoadBalanceEnv:
     (DESIGN.md §3.11).
     server_availability=True lets set_server_availability / set_cluster_sizes script which servers
     of each env are up; not with fail_prob > 0 (LbsimError, code ENOTSUP).
+    cross_traffic=True lets set_cross_traffic hide a share of each env's arrivals from the agent:
+    flows of another balancer that load the servers but appear in no observation column, score,
+    count or statistic; not with lost_fin_prob > 0 (LbsimError, code ENOTSUP).
+    Such an env steps through the full server-per-lane dynamics kernel, as a flow_stats one does.
     """
 
     def __init__(self, num_envs: int, num_servers: int = 4, *, device=None,
                  autoreset: bool = True, keep_terminal_obs: bool = False,
                  strict_actions: bool = False, feature_mode: str = "problem01",
                  graph_mode: bool = False, autoreset_mode: str = "same_step",
-                 flow_stats: bool = False, server_availability: bool = False, **kwargs):
+                 flow_stats: bool = False, server_availability: bool = False,
+                 cross_traffic: bool = False, **kwargs):
         torch = _torch()
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError(f"Unknown autoreset_mode: {autoreset_mode}")
@@ -590,6 +626,8 @@ class VecLoadBalanceEnv:
         self.server_availability = bool(server_availability)
         if server_availability:
             self.handle.enable_server_avail()
+        if cross_traffic:
+            self.handle.enable_cross_traffic()
         if self.trace is not None:
             if _is_bank(self.trace):
                 self.handle.set_trace_bank(self.trace)
@@ -826,6 +864,57 @@ class VecLoadBalanceEnv:
     def clear_rates(self) -> None:
         """Back to the config's shared arrival_rate / server_rates."""
         self.handle.clear_env_rates()
+
+    # ---- hidden cross traffic (cross_traffic=True; DESIGN.md §3.17)
+    def set_cross_traffic(self, share, weights=None) -> None:
+        """Per-env hidden cross traffic: share, a scalar or (B,), the probability in [0, 1] that
+        an arrival is a flow the agent's balancer did not forward; weights (S,) or (B, S), >= 0
+        with a positive sum per row, the distribution of such flows over the servers (None:
+        uniform).  Tensors or arrays on any device (cast to f32).  A hidden flow ignores the
+        action, queues and is served like any flow (dropped, and counted in info's dropped, at a
+        full or down server) and shows nowhere else: observation column 0, the SED / LSQ scores,
+        assign_counts, the reservoirs, the reward and the flow statistics see the visible flows
+        only.  The visible arrival rate is (1 - share) * arrival_rate: scale arrival_rate with
+        set_rates to keep it fixed.  From the next launch on (step, reset, warm-up); flows already
+        queued stay what they were.  A value out of range (NaN included): ValueError, the previous
+        values stay in force.  Not part of get_state(); a shard passes its own rows.  graph_mode:
+        calls rewrite the same device arrays, so replays see them
+        (marllb_amd.randomize.sample_cross_traffic draws such arrays)."""
+        torch = _torch()
+        B, S = self.num_envs, self.num_servers
+        sh = torch.as_tensor(share)
+        if sh.dim() > 1 or (sh.dim() == 1 and sh.shape[0] != B):
+            raise ValueError(f"share: expected a scalar or shape ({B},), got {tuple(sh.shape)}")
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(weights)
+            if tuple(w.shape) not in ((S,), (B, S)):
+                raise ValueError(f"weights: expected shape ({S},) or ({B}, {S}), got "
+                                 f"{tuple(w.shape)}")
+        rows = B if sh.dim() == 1 or (w is not None and w.dim() == 2) else 1
+        sh = sh.to(device=self.device, dtype=torch.float32).reshape(-1)
+        if sh.shape[0] != rows:
+            sh = sh.expand(rows)
+        if w is not None:
+            w = w.to(device=self.device, dtype=torch.float32).reshape(-1, S)
+            if w.shape[0] != rows:
+                w = w.expand(rows, S)
+            w = w.contiguous()
+        self.handle.set_cross_traffic(sh.contiguous(), w, rows=rows)
+
+    def clear_cross_traffic(self) -> None:
+        """Every share back to 0 (the hidden weights stay)."""
+        self.handle.clear_cross_traffic()
+
+    @property
+    def cross_traffic(self):
+        """(share (B,), weights (B, S)) f32 device tensors: the values in force, as the simulator
+        holds them -- 24-bit fixed point, each row of weights normalised to sum 1."""
+        torch = _torch()
+        thr, cum = self.handle.cross_traffic()
+        edges = torch.cat([torch.zeros_like(cum[:, :1]), cum], dim=1).to(torch.float64)
+        return ((thr.to(torch.float64) / 16777216.0).to(torch.float32),
+                ((edges[:, 1:] - edges[:, :-1]) / 16777216.0).to(torch.float32))
 
     @property
     def rates(self):
@@ -1591,6 +1680,26 @@ class LoadBalanceEnv:
 
     def clear_flow_stats(self) -> None:
         self._flow_vec().clear_flow_stats()
+
+    # ---- hidden cross traffic (LoadBalanceEnv(cross_traffic=True))
+    def _cross_vec(self) -> "VecLoadBalanceEnv":
+        if self._vec is None:
+            raise RuntimeError("cross traffic needs the GPU simulator (not reference_plumbing)")
+        return self._vec
+
+    def set_cross_traffic(self, share: float, weights=None) -> None:
+        """The share of hidden arrivals and their weights (num_servers,) over the servers
+        (VecLoadBalanceEnv.set_cross_traffic of the one env)."""
+        self._cross_vec().set_cross_traffic(float(share), weights)
+
+    @property
+    def cross_traffic(self):
+        """(share, weights) in force: a float and a list of num_servers floats."""
+        sh, w = self._cross_vec().cross_traffic
+        return float(sh[0]), w[0].cpu().tolist()
+
+    def clear_cross_traffic(self) -> None:
+        self._cross_vec().clear_cross_traffic()
 
     # ---- workload tables (VecLoadBalanceEnv.set_workload_tables of the one env)
     def _work_vec(self) -> "VecLoadBalanceEnv":

@@ -231,6 +231,18 @@ class VecMultiAgentLoadBalanceEnv:
     def clear_rates(self) -> None:
         self.vec.clear_rates()
 
+    def set_cross_traffic(self, share, weights=None) -> None:
+        """Hidden cross traffic: VecLoadBalanceEnv.set_cross_traffic (an env made with
+        cross_traffic=True; weights over the S = num_agents * servers_per_agent servers)."""
+        self.vec.set_cross_traffic(share, weights)
+
+    @property
+    def cross_traffic(self):
+        return self.vec.cross_traffic
+
+    def clear_cross_traffic(self) -> None:
+        self.vec.clear_cross_traffic()
+
     @property
     def rates(self):
         return self.vec.rates

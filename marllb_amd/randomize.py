@@ -224,3 +224,39 @@ def rolling_restart_schedule(num_servers: int, phases: int, *, device=None):
     j = torch.arange(P)
     down = (torch.arange(S)[None, :] == (j % S)[:, None]) & (j > 0)[:, None]
     return (~down).to(device=device, dtype=torch.uint8)
+
+
+# ---- hidden cross traffic (VecLoadBalanceEnv.set_cross_traffic)
+
+def sample_cross_traffic(num_envs: int, num_servers: int, *, share=(0.0, 0.5), skew=(1.0, 4.0),
+                         generator=None, device=None):
+    """-> (share (B,), weights (B, S)) float32 tensors for VecLoadBalanceEnv.set_cross_traffic.
+
+    share (lo, hi): each env's hidden share, uniform in [lo, hi], 0 <= lo <= hi <= 1.
+    skew (lo, hi): each env's ratio r, uniform in [lo, hi], 1 <= lo <= hi; its hidden weights are
+    a random permutation of the geometric ladder 1, 1/r, ..., r^-(S-1) (another balancer favouring
+    some servers; r = 1: uniform).
+    generator: a torch.Generator (the draws are made on its device, then moved to `device`).
+    The visible arrival rate of env b is (1 - share[b]) * its arrival rate: to keep it at `rate`,
+    give set_rates the arrival rate rate / (1 - share).
+    """
+    import torch
+
+    B, S = int(num_envs), int(num_servers)
+    if B < 1 or S < 1:
+        raise ValueError(f"need num_envs >= 1 and num_servers >= 1 (got {num_envs}, {num_servers})")
+    if not 0.0 <= float(share[0]) <= float(share[1]) <= 1.0:
+        raise ValueError(f"share: need 0 <= lo <= hi <= 1 (got {share[0]}, {share[1]})")
+    if not (1.0 <= float(skew[0]) <= float(skew[1])) or not math.isfinite(float(skew[1])):
+        raise ValueError(f"skew: need 1 <= lo <= hi (got {skew[0]}, {skew[1]})")
+    gdev = generator.device if generator is not None else torch.device("cpu")
+
+    def uniform(shape, lo, hi):
+        u = torch.rand(shape, generator=generator, device=gdev, dtype=torch.float64)
+        return float(lo) + (float(hi) - float(lo)) * u
+
+    sh = uniform((B,), share[0], share[1]).clamp(0.0, 1.0)
+    r = uniform((B,), skew[0], skew[1])
+    rank = torch.rand((B, S), generator=generator, device=gdev).argsort(dim=1).to(torch.float64)
+    w = torch.pow(r.unsqueeze(1), -rank)
+    return (sh.to(device=device, dtype=torch.float32), w.to(device=device, dtype=torch.float32))
