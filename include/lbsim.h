@@ -703,6 +703,39 @@ int lbsim_set_cross_traffic(lbsim_t* h, const float* share, const float* weight,
 int lbsim_get_cross_traffic(lbsim_t* h, uint32_t* thr_out, uint32_t* cum_out, void* stream);
 int lbsim_clear_cross_traffic(lbsim_t* h, void* stream);
 
+/* ---- multi-worker servers (per-server worker counts) ----
+ * On an enabled handle server s of env b has c = workers[b, s] identical workers, 1 <= c <= 64,
+ * behind one FCFS queue; server_rate stays the rate of ONE worker (capacity c * mu).  The queue
+ * entries are kept in non-decreasing completion order (a new entry after every equal or smaller
+ * one); an arrival at ta that finds n flows queued starts at ta if n < c, else at
+ * max(ta, completion of the entry at sorted position n - c).  c = 1 is the single FIFO pipe, bit
+ * for bit.  Column 0, assign counts, dropped, eligibility and the flow statistics are defined as
+ * before (flows in the system, in service included); a server's reservoir receives, per launch,
+ * its carried-in completions in completion order and then the flows that arrive and complete in
+ * the step in arrival order.
+ * lbsim_server_workers_enable: before the handle's first lbsim_reset (LBSIM_EINVAL after it; a
+ * second call is a no-op).  LBSIM_ENOTSUP on a handle with lost_fin_prob > 0 or duration_mode
+ * SERVICE.  Allocates workers[B, S] (every count 1; never moved) and makes the handle a full one
+ * (dynamics_group_full_kernel, two launches).  With every count 1 results equal a handle that was
+ * not enabled.
+ * lbsim_set_server_workers: workers[rows, S] int32, a DEVICE pointer, rows = 1 (every env the
+ * same) or B (LBSIM_ESHAPE otherwise).  Validated on the device into a staging copy; the call
+ * waits on `stream`, and with any count outside [1, 64] returns LBSIM_EINVAL (the count of
+ * offenders in lbsim_last_error) and leaves what was in force untouched.  The array is rewritten
+ * in place: a step captured into a hipGraph sees later values.  New counts apply to arrivals
+ * assigned from the next launch on (a reset's warm-up included); queued flows keep their
+ * completion times, and the c queued flows with the latest completions are taken to hold the
+ * workers (exact while c is constant since a reset, an approximation after a change).  Not part
+ * of the snapshot; a shard passes its own rows.
+ * lbsim_get_server_workers: workers_out[B, S] int32 (DEVICE), asynchronous on `stream`.
+ * lbsim_clear_server_workers: every count 1, in place, asynchronous on `stream`.
+ * set / get / clear return LBSIM_EINVAL on a handle that was not enabled.  lbsim_step and
+ * lbsim_reset gain no allocation and no synchronisation. */
+int lbsim_server_workers_enable(lbsim_t* h);
+int lbsim_set_server_workers(lbsim_t* h, const int32_t* workers, int32_t rows, void* stream);
+int lbsim_get_server_workers(lbsim_t* h, int32_t* workers_out, void* stream);
+int lbsim_clear_server_workers(lbsim_t* h, void* stream);
+
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/
  * alias_table.h:82-158, alias_table_build, rebuilt by lb_rl_node.c:92-111 from the weights the

@@ -193,6 +193,10 @@ _SIGNATURES = {
     "lbsim_set_cross_traffic": (ctypes.c_int, [_P, _P, _P, ctypes.c_int32, _P]),
     "lbsim_get_cross_traffic": (ctypes.c_int, [_P, _P, _P, _P]),
     "lbsim_clear_cross_traffic": (ctypes.c_int, [_P, _P]),
+    "lbsim_server_workers_enable": (ctypes.c_int, [_P]),
+    "lbsim_set_server_workers": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P]),
+    "lbsim_get_server_workers": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_clear_server_workers": (ctypes.c_int, [_P, _P]),
     "lbsim_server_avail_enable": (ctypes.c_int, [_P]),
     "lbsim_set_server_avail": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_int32, _P]),

@@ -17,6 +17,7 @@
 #include <vector>
 
 #define LBSIM_CROSS_KERNELS  // cross_convert_kernel is defined in this object (lbsim_cross.h)
+#define LBSIM_WORKERS_KERNELS  // and workers_convert_kernel (lbsim_workers.h)
 #include "../../include/lbsim.h"
 #include "lbsim_avail.h"
 #include "lbsim_internal.h"
@@ -118,6 +119,11 @@ struct lbsim {
   // converts into these and only a valid one is copied over the live arrays), the offender count
   void* cross_buf = nullptr;
   CrossTraffic cross{};  // the live arrays (null pointers: the handle has no cross traffic)
+  // lbsim_server_workers_enable: one block of 32-bit words, allocated once and never moved -- the
+  // live c[B*S] the full dynamics kernel reads (ServerWorkers), its staging copy and the
+  // offender count
+  void* workers_buf = nullptr;
+  ServerWorkers workers{};  // the live array (a null pointer: every server one FIFO pipe)
   bool initialised;  // a full reset has been issued
   bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
@@ -1098,7 +1104,9 @@ std::string short_kernel_name(const char* raw) {
   return s;
 }
 
-LaunchCtx ctx(const lbsim_t* h) { return LaunchCtx{h->plan, h->st, h->prm, h->flow, h->cross}; }
+LaunchCtx ctx(const lbsim_t* h) {
+  return LaunchCtx{h->plan, h->st, h->prm, h->flow, h->cross, h->workers};
+}
 
 // The handle's plan: the process's overrides are read on the first call and kept.
 StepPlan plan_of(const lbsim_t* h) {
@@ -1112,6 +1120,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.flow_stats = h->flow.hist != nullptr;
   in.work_tables = h->wtab_T > 0;
   in.cross_traffic = h->cross_buf != nullptr;
+  in.server_workers = h->workers_buf != nullptr;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -1292,6 +1301,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->sched_buf) (void)hipFree(h->sched_buf);
     if (h->flow_buf) (void)hipFree(h->flow_buf);
     if (h->cross_buf) (void)hipFree(h->cross_buf);
+    if (h->workers_buf) (void)hipFree(h->workers_buf);
     if (h->avail_buf) (void)hipFree(h->avail_buf);
     if (h->wtab_buf) (void)hipFree(h->wtab_buf);
     for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
@@ -2066,6 +2076,102 @@ int lbsim_clear_cross_traffic(lbsim_t* h, void* stream) {
   if (hipMemsetAsync(h->cross.thr, 0, (size_t)h->B * 4, (hipStream_t)stream) != hipSuccess)
     return fail(h, LBSIM_EDEVICE, "cross traffic: hipMemsetAsync failed");
   return LBSIM_OK;
+}
+
+// ---- multi-worker servers (the rule and the conversion kernel: lbsim_workers.h)
+
+int lbsim_server_workers_enable(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->workers_buf != nullptr) return LBSIM_OK;
+  if (h->prm.lf_thr != 0u)
+    return fail(h, LBSIM_ENOTSUP, "server workers on a lost-FIN handle (lost_fin_prob > 0): the "
+                                  "pending guesses rely on completion times that do not decrease "
+                                  "in arrival order");
+  if (h->prm.dur_service != 0)
+    return fail(h, LBSIM_ENOTSUP, "server workers with duration_mode SERVICE: a carried-in "
+                                  "flow's service time is not tc - max(ta, its predecessor's tc) "
+                                  "on a multi-worker server, and the ring does not hold it");
+  if (h->reset_seen)
+    return fail(h, LBSIM_EINVAL, "lbsim_server_workers_enable must precede the handle's first "
+                                 "lbsim_reset (it changes which kernels the handle launches)");
+  DeviceGuard g(h->device);
+  const size_t BS = (size_t)h->B * h->S, words = 2 * BS + 1;
+  void* p = nullptr;
+  if (hipMalloc(&p, words * 4) != hipSuccess)
+    return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", words * 4);
+  int32_t* const w = (int32_t*)p;
+  bool ok = hipMemset(p, 0, words * 4) == hipSuccess;
+  if (ok) {  // every count 1 in the live array
+    hipLaunchKernelGGL(workers_convert_kernel, dim3((unsigned)((BS + 255) / 256)), dim3(256), 0,
+                       nullptr, (const int32_t*)nullptr, 1, (int64_t)BS, h->S, w,
+                       (uint32_t*)(w + 2 * BS));
+    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+  }
+  if (!ok) {
+    (void)hipFree(p);
+    return fail(h, LBSIM_EDEVICE, "server workers: device init failed");
+  }
+  h->workers_buf = p;
+  h->workers.c = w;
+  h->plan = plan_of(h);  // a server-workers handle is a full handle (make_plan)
+  return LBSIM_OK;
+}
+
+int lbsim_set_server_workers(lbsim_t* h, const int32_t* workers, int32_t rows, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->workers_buf == nullptr)
+    return fail(h, LBSIM_EINVAL, "server workers are off: call lbsim_server_workers_enable first");
+  if (workers == nullptr) return fail(h, LBSIM_EINVAL, "server workers: workers is NULL");
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "server workers: rows must be 1 or num_envs = %d (got %d)", h->B,
+                rows);
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t BS = (size_t)h->B * h->S;
+  int32_t* const live = (int32_t*)h->workers_buf;
+  int32_t* const stg = live + BS;
+  uint32_t* const bad = (uint32_t*)(live + 2 * BS);
+  if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "server workers: hipMemsetAsync failed");
+  hipLaunchKernelGGL(workers_convert_kernel, dim3((unsigned)((BS + 255) / 256)), dim3(256), 0, s,
+                     workers, (int)rows, (int64_t)BS, h->S, stg, bad);
+  const int rc = launch_check(h, "workers_convert_kernel");
+  if (rc != LBSIM_OK) return rc;
+  uint32_t nbad = 0;
+  if (hipMemcpyAsync(&nbad, bad, sizeof(nbad), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "server workers: conversion failed");
+  if (nbad != 0u)  // the live array is untouched: the previous counts stay in force
+    return fail(h, LBSIM_EINVAL, "server workers: %u count(s) outside [1, %d]", nbad,
+                (int)kMaxWorkers);
+  if (hipMemcpyAsync(live, stg, BS * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "server workers: device copy failed");
+  return LBSIM_OK;
+}
+
+int lbsim_get_server_workers(lbsim_t* h, int32_t* workers_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->workers_buf == nullptr)
+    return fail(h, LBSIM_EINVAL, "server workers are off: call lbsim_server_workers_enable first");
+  if (workers_out == nullptr) return fail(h, LBSIM_EINVAL, "server workers: workers_out is NULL");
+  DeviceGuard g(h->device);
+  if (hipMemcpyAsync(workers_out, h->workers.c, (size_t)h->B * h->S * 4, hipMemcpyDeviceToDevice,
+                     (hipStream_t)stream) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "server workers: device copy failed");
+  return LBSIM_OK;
+}
+
+int lbsim_clear_server_workers(lbsim_t* h, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->workers_buf == nullptr)
+    return fail(h, LBSIM_EINVAL, "server workers are off: call lbsim_server_workers_enable first");
+  DeviceGuard g(h->device);
+  const size_t BS = (size_t)h->B * h->S;
+  int32_t* const live = (int32_t*)h->workers_buf;
+  hipLaunchKernelGGL(workers_convert_kernel, dim3((unsigned)((BS + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const int32_t*)nullptr, 1, (int64_t)BS, h->S, live,
+                     (uint32_t*)(live + 2 * BS));
+  return launch_check(h, "workers_convert_kernel");
 }
 
 int lbsim_server_avail_enable(lbsim_t* h) {

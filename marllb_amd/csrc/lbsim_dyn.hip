@@ -52,7 +52,7 @@ void launch_dynamics_t(const LaunchCtx& L, const void* action, int dtype, int32_
       constexpr bool TRACE = decltype(T)::value;
       if (d.full) {  // every feature's code (group_event_loop FULL), its own register budget
         LBSIM_LAUNCH((dynamics_group_full_kernel<G, MODE, POLICY, TRACE>), grid, block, 0, stream,
-                     L.st, prm, action, dtype, assign, mask, L.flow, L.cross);
+                     L.st, prm, action, dtype, assign, mask, L.flow, L.cross, L.workers);
         return;
       }
       // the register budgets that exist: 4 waves for every next-step auto-reset step, 1 for the

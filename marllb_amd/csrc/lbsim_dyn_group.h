@@ -28,6 +28,7 @@
 
 #include "lbsim_cross.h"
 #include "lbsim_kernels.h"
+#include "lbsim_workers.h"
 
 namespace lbk {
 
@@ -158,6 +159,41 @@ __device__ __forceinline__ void flow_stats_add(SrvLane& V, uint32_t fct) {
 struct CrossLane {
   bool on = false;
   uint32_t thr = 0u, edge = 0u, salt = 0u;
+};
+
+// Multi-worker servers (lbsim_workers.h) as a lane of a full handle sees them:
+// its own server's worker count, read once in the wave's prologue.  on: the handle has the array
+// (wave-uniform: the kernel's argument).
+struct WorkLane {
+  bool on = false;
+  int32_t c = 1;
+};
+
+// The lane's queue by position from the head (lbsim_workers.h's accessor): the LDS window below
+// kGroupWL, the HBM ring from there on.  Window and ring accesses stay in separate branches, the
+// ring's fenced as at the push site: no flat access (see dynamics_kernel).
+struct LaneQueue {
+  int2* win;   // the wave's windows, [slot][lane]
+  int2* ring;  // this server's ring
+  int lane, lh, head, Q;
+  __device__ __forceinline__ int2 get(int pos) const {
+    int2 e;
+    if (workers_in_window(pos, kGroupWL)) {
+      e = win[workers_win_slot(lh, pos, kGroupWL) * 64 + lane];
+    } else {
+      e = ring[(uint32_t)workers_ring_index(head, pos, Q)];
+      asm volatile("");
+    }
+    return e;
+  }
+  __device__ __forceinline__ void set(int pos, const int2& e) const {
+    if (workers_in_window(pos, kGroupWL)) {
+      win[workers_win_slot(lh, pos, kGroupWL) * 64 + lane] = e;
+    } else {
+      ring[(uint32_t)workers_ring_index(head, pos, Q)] = e;
+      asm volatile("");
+    }
+  }
 };
 
 // ALIAS table of the group in LDS: word f of active position k at [f][gbase + k].  Every lane of
@@ -306,7 +342,8 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
                                                  int2* const my_ring, bool fs_on = false,
                                                  const TraceSel& ts = TraceSel{},
                                                  const WorkSel& ws = WorkSel{},
-                                                 const CrossLane& cx = CrossLane{}) {
+                                                 const CrossLane& cx = CrossLane{},
+                                                 const WorkLane& wk = WorkLane{}) {
   constexpr int WL = kGroupWL;
   constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
   constexpr bool alias = POLICY == kPolicyAlias;
@@ -475,7 +512,17 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
     const bool mine = push && s == chosen;
 
     // ---- FIFO service on the chosen server (its lane)
-    const int32_t start_a = V.cnt > 0 ? (V.tail > ta ? V.tail : ta) : ta;
+    int32_t start_a = V.cnt > 0 ? (V.tail > ta ? V.tail : ta) : ta;
+    if constexpr (FULL) {
+      // multi-worker servers (§3.18): the queue is sorted by tc and the c latest completions hold
+      // the workers, so the flow starts when the entry at position cnt - c completes (at once
+      // with fewer than c queued).  c = 1: that entry is the tail, the line above.  Only the
+      // chosen lane reads it.
+      if (wk.on) {
+        if (mine && wk.c > 1)
+          start_a = workers_start(LaneQueue{win, my_ring, lane, V.lh, V.head, Q}, V.cnt, wk.c, ta);
+      }
+    }
     int32_t svc = (int32_t)(E.next_work * V.scale);
     svc = svc < 1 ? 1 : svc;
     const int32_t tc_a = start_a + svc;
@@ -511,15 +558,32 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
     // 65536 x 4, profiles/r06e/)
     if (mine) {
       const int2 e = make_int2(tc_a, FULL ? (hid ? kHiddenTa : ta) : ta);  // (hidden: the flag)
-      if (V.cnt < WL) {
-        *wslot((V.lh + V.cnt) & (WL - 1)) = e;
-      } else {
-        int pos = V.head + V.cnt;
-        pos = pos >= Q ? pos - Q : pos;
-        my_ring[(uint32_t)pos] = e;
-        asm volatile("");  // no flat store (see dynamics_kernel)
+      bool sorted = false;
+      if constexpr (FULL) {
+        // multi-worker servers (§3.18): the entry goes after every one with an equal or smaller
+        // tc, at most c - 1 entries moving up (a hidden flow's flag moves with its entry);
+        // the head time follows an insert at position 0, the tail is the latest completion
+        if (wk.on) {
+          if (wk.c > 1) {
+            sorted = true;
+            const int at =
+                workers_insert(LaneQueue{win, my_ring, lane, V.lh, V.head, Q}, V.cnt, e);
+            V.head_tc = at == 0 ? tc_a : V.head_tc;
+            V.tail = (V.cnt > 0 && V.tail > tc_a) ? V.tail : tc_a;
+          }
+        }
       }
-      V.tail = tc_a;
+      if (!sorted) {
+        if (V.cnt < WL) {
+          *wslot((V.lh + V.cnt) & (WL - 1)) = e;
+        } else {
+          int pos = V.head + V.cnt;
+          pos = pos >= Q ? pos - Q : pos;
+          my_ring[(uint32_t)pos] = e;
+          asm volatile("");  // no flat store (see dynamics_kernel)
+        }
+        V.tail = tc_a;
+      }
       if constexpr (FULL) {  // (a hidden flow: no assignment, one more in the hidden count)
         V.assigned += hid ? 0 : 1;
         V.lost -= hid ? 1 : 0;
@@ -552,7 +616,8 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                                                int2* win, int32_t* atab, int4* acache,
                                                bool fs_on = false,
                                                const TraceSel& ts = TraceSel{},
-                                               const CrossLane& cx = CrossLane{}) {
+                                               const CrossLane& cx = CrossLane{},
+                                               const WorkLane& wk = WorkLane{}) {
   constexpr int WL = kGroupWL;
   const int S = p.S, Q = p.Q;
   const int32_t dt = p.dt_us;
@@ -683,7 +748,8 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
     group_event_loop<G, POLICY, TRACE, false, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                                    acache, my_res, my_ring, fs_on, ts, ws, cx);
+                                                    acache, my_res, my_ring, fs_on, ts, ws, cx,
+                                                    wk);
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
   } else if (__all(finite)) {
@@ -740,7 +806,8 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
                                                int32_t* assign_out, const uint8_t* reset_mask,
                                                uint32_t wave, int lane, DynGroupLds<POLICY>& L,
                                                const FlowStats& fs = FlowStats{},
-                                               const CrossTraffic& ct = CrossTraffic{}) {
+                                               const CrossTraffic& ct = CrossTraffic{},
+                                               const ServerWorkers& sw = ServerWorkers{}) {
   static_assert(G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64,
                 "group = a power of two lanes of the wave");
   constexpr int WL = kGroupWL;
@@ -798,6 +865,13 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
       cx.on = true;
       cx.thr = ct.thr[b];
       cx.edge = V.act ? ct.cum[sb] : kCrossOne;
+    }
+  }
+  WorkLane wk;  // multi-worker servers: this lane's own server's count, one coalesced load
+  if constexpr (FULL) {
+    if (sw.c != nullptr) {  // wave-uniform
+      wk.on = true;
+      wk.c = V.act ? sw.c[sb] : 1;
     }
   }
 
@@ -940,13 +1014,13 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     load_in();
     cross_in();
     sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w_own, wall, win, atab,
-                                           acache, fs_on, ts, cx);
+                                           acache, fs_on, ts, cx, wk);
   } else if constexpr (MODE == kModeReset) {
     reset_in();
     cross_in();
     for (int k = 0; k < p.warmup_steps; ++k)
       sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, 1.0f, wall, win, atab,
-                                             acache, fs_on, ts, cx);
+                                             acache, fs_on, ts, cx, wk);
     reset_out(0);
   } else {
     // kModeStepNR (next-step auto-reset): an env whose last step returned done resets in place of
@@ -963,7 +1037,7 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     const float w = rs ? 1.0f : w_own;
     for (int k = 0; k < nsteps; ++k)
       sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w, wall, win, atab,
-                                             acache, fs_on, ts, cx);
+                                             acache, fs_on, ts, cx, wk);
     if (rs) reset_out(-1);
   }
 
@@ -1031,15 +1105,17 @@ __global__ void __launch_bounds__(64, WAVES)
 // The same for a full handle (group_event_loop's FULL: n_flow_on_mode VPP, a duration plane,
 // lost-FIN deferral, reservoir_mode VPP, flow statistics): the general event loop with every
 // feature, on its own register budget.  fs: the flow statistics' arrays (null pointers: off); ct:
-// the cross traffic's (lbsim_cross.h; null pointers: the handle has none).
+// the cross traffic's (lbsim_cross.h; null pointers: the handle has none); sw: the servers'
+// worker counts (lbsim_workers.h; a null pointer: every server one FIFO pipe).
 template <int G, int MODE, int POLICY, bool TRACE>
 __global__ void __launch_bounds__(64)
     dynamics_group_full_kernel(DevState st, SimParams p, const void* action, int action_dtype,
                                int32_t* assign_out, const uint8_t* reset_mask, FlowStats fs,
-                               CrossTraffic ct) {
+                               CrossTraffic ct, ServerWorkers sw) {
   __shared__ DynGroupLds<POLICY> L;
   dyn_group_wave<G, MODE, POLICY, TRACE, true>(st, p, action, action_dtype, assign_out,
-                                               reset_mask, blockIdx.x, (int)threadIdx.x, L, fs, ct);
+                                               reset_mask, blockIdx.x, (int)threadIdx.x, L, fs, ct,
+                                               sw);
 }
 
 }  // namespace lbk

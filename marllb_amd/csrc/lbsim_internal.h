@@ -2,6 +2,7 @@
 // units that instantiate the templated kernels (compiled in parallel, linked into liblbsim.so):
 //
 //   lbsim_cross.h      hidden cross traffic: the host / device rule and its conversion kernel
+//   lbsim_workers.h    multi-worker servers: the host / device rule and its conversion kernel
 //   lbsim_plan.h       make_plan: which kernels a handle's step and reset launch, decided once
 //                      (host-only; the launchers below turn the plan into template arguments)
 //   lbsim_dyn.hip      dynamics_kernel / dynamics_group_kernel launchers; built three times
@@ -22,6 +23,7 @@
 #include "lbsim_cross.h"
 #include "lbsim_kernels.h"
 #include "lbsim_plan.h"
+#include "lbsim_workers.h"
 
 namespace lbk {
 
@@ -51,6 +53,7 @@ struct LaunchCtx {
   const SimParams& prm;
   const FlowStats& flow;  // the full group dynamics' flow statistics (null pointers: off)
   const CrossTraffic& cross;  // and its cross traffic (lbsim_cross.h; null pointers: none)
+  const ServerWorkers& workers;  // and its servers' worker counts (lbsim_workers.h; null: none)
 };
 
 // Runtime value -> template argument: pick<2, 4, 8>(v, f) calls f(std::integral_constant<int, v>)

@@ -488,6 +488,33 @@ class Handle:
         """Every share 0 (lbsim_clear_cross_traffic), on the current stream."""
         self.check(self.lib.lbsim_clear_cross_traffic(self.h, ctypes.c_void_p(self._stream())))
 
+    def enable_server_workers(self) -> None:
+        """Multi-worker servers from now on (lbsim_server_workers_enable): before the handle's
+        first reset (ValueError after it); LbsimError ENOTSUP with lost_fin_prob > 0 or
+        duration_mode="service"."""
+        self.check(self.lib.lbsim_server_workers_enable(self.h))
+
+    def set_server_workers(self, workers, *, rows: int) -> None:
+        """Worker counts (lbsim_set_server_workers): workers (rows, S) int32 contiguous on the
+        handle's device, rows = 1 or B."""
+        self.check(self.lib.lbsim_set_server_workers(
+            self.h, ctypes.c_void_p(workers.data_ptr()), int(rows),
+            ctypes.c_void_p(self._stream())))
+
+    def server_workers(self):
+        """(B, S) int32 device tensor: the worker counts in force (lbsim_get_server_workers)."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device_index)
+        out = torch.empty((int(self.cfg.num_envs), int(self.cfg.num_servers)), dtype=torch.int32,
+                          device=dev)
+        self.check(self.lib.lbsim_get_server_workers(self.h, ctypes.c_void_p(out.data_ptr()),
+                                                     ctypes.c_void_p(self._stream())))
+        return out
+
+    def clear_server_workers(self) -> None:
+        """Every count 1 (lbsim_clear_server_workers), on the current stream."""
+        self.check(self.lib.lbsim_clear_server_workers(self.h, ctypes.c_void_p(self._stream())))
+
     def enable_server_avail(self) -> None:
         """Scripted server availability from now on (lbsim_server_avail_enable): before the
         handle's first reset (ValueError after it); LbsimError ENOTSUP with fail_prob > 0."""
@@ -580,6 +607,11 @@ class VecLoadBalanceEnv:
     flows of another balancer that load the servers but appear in no observation column, score,
     count or statistic; not with lost_fin_prob > 0 (LbsimError, code ENOTSUP).
     Such an env steps through the full server-per-lane dynamics kernel, as a flow_stats one does.
+    server_workers=True lets set_server_workers give each server its own number of workers (an
+    array: enabled, and those counts set): c workers of rate server_rate each behind one FCFS
+    queue, so flows are served side by side and a short one overtakes a long one (DESIGN.md
+    §3.18); not with lost_fin_prob > 0 or duration_mode="service" (LbsimError, code ENOTSUP).
+    Such an env steps through the full server-per-lane dynamics kernel too.
     """
 
     def __init__(self, num_envs: int, num_servers: int = 4, *, device=None,
@@ -587,7 +619,7 @@ class VecLoadBalanceEnv:
                  strict_actions: bool = False, feature_mode: str = "problem01",
                  graph_mode: bool = False, autoreset_mode: str = "same_step",
                  flow_stats: bool = False, server_availability: bool = False,
-                 cross_traffic: bool = False, **kwargs):
+                 cross_traffic: bool = False, server_workers=False, **kwargs):
         torch = _torch()
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError(f"Unknown autoreset_mode: {autoreset_mode}")
@@ -628,6 +660,10 @@ class VecLoadBalanceEnv:
             self.handle.enable_server_avail()
         if cross_traffic:
             self.handle.enable_cross_traffic()
+        if server_workers is not False and server_workers is not None:
+            self.handle.enable_server_workers()
+            if server_workers is not True:
+                self.set_server_workers(server_workers)
         if self.trace is not None:
             if _is_bank(self.trace):
                 self.handle.set_trace_bank(self.trace)
@@ -915,6 +951,40 @@ class VecLoadBalanceEnv:
         edges = torch.cat([torch.zeros_like(cum[:, :1]), cum], dim=1).to(torch.float64)
         return ((thr.to(torch.float64) / 16777216.0).to(torch.float32),
                 ((edges[:, 1:] - edges[:, :-1]) / 16777216.0).to(torch.float32))
+
+    # ---- multi-worker servers (server_workers=True)
+    def set_server_workers(self, workers) -> None:
+        """Per-server worker counts: workers (S,) or (B, S) integers in [1, 64], a tensor or array
+        on any device.  Server s of env b then serves up to workers[b, s] flows side by side, each
+        at the rate server_rate of ONE worker (capacity c * server_rate: divide the rates by c
+        with set_rates to compare at equal capacity; marllb_amd.randomize.sample_server_workers
+        draws both).  Column 0, assign_counts and dropped count as before.  From the next launch on
+        (step, reset, warm-up); queued flows keep their completion times.  A count out of range,
+        or a non-integer one: ValueError, the previous counts stay in force.  Not part of
+        get_state(); a shard passes its own rows.  graph_mode: calls rewrite the same device
+        array, so replays see them."""
+        torch = _torch()
+        B, S = self.num_envs, self.num_servers
+        w = torch.as_tensor(workers)
+        if tuple(w.shape) not in ((S,), (B, S)):
+            raise ValueError(f"workers: expected shape ({S},) or ({B}, {S}), got {tuple(w.shape)}")
+        if w.is_floating_point():
+            if not bool((w == w.round()).all()):  # (NaN included)
+                raise ValueError("workers: expected integers")
+        elif w.dtype == torch.bool:
+            raise ValueError("workers: expected integers")
+        # out-of-range counts stay out of range as int32 (the device call rejects them)
+        w = w.to(torch.float64).clamp(-1.0, 65.0).to(device=self.device, dtype=torch.int32)
+        rows = B if w.dim() == 2 else 1
+        self.handle.set_server_workers(w.reshape(rows, S).contiguous(), rows=rows)
+
+    def get_server_workers(self):
+        """(B, S) int32 device tensor: the worker counts in force."""
+        return self.handle.server_workers()
+
+    def clear_server_workers(self) -> None:
+        """Every server back to one worker."""
+        self.handle.clear_server_workers()
 
     @property
     def rates(self):
@@ -1700,6 +1770,26 @@ class LoadBalanceEnv:
 
     def clear_cross_traffic(self) -> None:
         self._cross_vec().clear_cross_traffic()
+
+    # ---- multi-worker servers (LoadBalanceEnv(server_workers=[...] or True))
+    def _workers_vec(self) -> "VecLoadBalanceEnv":
+        if self._vec is None:
+            raise RuntimeError("server workers need the GPU simulator (not reference_plumbing)")
+        return self._vec
+
+    def set_server_workers(self, workers) -> None:
+        """The servers' worker counts, (num_servers,) integers in [1, 64]
+        (VecLoadBalanceEnv.set_server_workers of the one env)."""
+        w = np.asarray(workers)
+        if w.shape != (self.num_servers,):
+            raise ValueError(f"workers: expected ({self.num_servers},), got {w.shape}")
+        self._workers_vec().set_server_workers(w)
+
+    def get_server_workers(self) -> List[int]:
+        return self._workers_vec().get_server_workers()[0].cpu().tolist()
+
+    def clear_server_workers(self) -> None:
+        self._workers_vec().clear_server_workers()
 
     # ---- workload tables (VecLoadBalanceEnv.set_workload_tables of the one env)
     def _work_vec(self) -> "VecLoadBalanceEnv":

@@ -240,6 +240,18 @@ class VecMultiAgentLoadBalanceEnv:
     def cross_traffic(self):
         return self.vec.cross_traffic
 
+    def set_server_workers(self, workers) -> None:
+        """Per-server worker counts, (S,) or (B, S) over S = num_agents * servers_per_agent
+        servers in agent order: VecLoadBalanceEnv.set_server_workers (an env made with
+        server_workers=True)."""
+        self.vec.set_server_workers(workers)
+
+    def get_server_workers(self):
+        return self.vec.get_server_workers()
+
+    def clear_server_workers(self) -> None:
+        self.vec.clear_server_workers()
+
     def clear_cross_traffic(self) -> None:
         self.vec.clear_cross_traffic()
 

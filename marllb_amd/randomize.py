@@ -260,3 +260,40 @@ def sample_cross_traffic(num_envs: int, num_servers: int, *, share=(0.0, 0.5), s
     rank = torch.rand((B, S), generator=generator, device=gdev).argsort(dim=1).to(torch.float64)
     w = torch.pow(r.unsqueeze(1), -rank)
     return (sh.to(device=device, dtype=torch.float32), w.to(device=device, dtype=torch.float32))
+
+
+# ---- multi-worker servers (VecLoadBalanceEnv.set_server_workers)
+
+SERVER_RANGE = (1.0, 1.0e7)  # flows/s, make_config's range for a server rate
+
+
+def sample_server_workers(num_envs: int, num_servers: int, choices=(1, 2, 4), seed: int = 0,
+                          keep_capacity: bool = True, *, server_rates=None, device=None):
+    """-> (workers (B, S) int32, server_rate (B, S) float32) for
+    VecLoadBalanceEnv.set_server_workers and set_rates(None, server_rate).
+
+    workers: each server's count, uniform over `choices` (integers in [1, 64]).
+    server_rate: the rate of ONE worker.  server_rates (a scalar, (S,) or (B, S), flows/s; default
+    100) is each server's rate before the split; with keep_capacity it is divided by the server's
+    count, so "one fast core against several slow ones" is compared at equal capacity c * mu;
+    without, every worker keeps it and a server of c workers has c times the capacity.  Clamped to
+    make_config's range for a server rate.  Deterministic for a seed."""
+    import torch
+
+    B, S = int(num_envs), int(num_servers)
+    ch = [int(c) for c in choices]
+    if B < 1 or S < 1:
+        raise ValueError(f"need num_envs >= 1 and num_servers >= 1 (got {num_envs}, {num_servers})")
+    if not ch or any(c != x for c, x in zip(ch, choices)) or min(ch) < 1 or max(ch) > 64:
+        raise ValueError(f"choices: need integers in [1, 64] (got {tuple(choices)})")
+    g = torch.Generator().manual_seed(int(seed))
+    pick = torch.randint(0, len(ch), (B, S), generator=g, dtype=torch.int64)
+    workers = torch.tensor(ch, dtype=torch.int64)[pick]
+    base = torch.as_tensor(100.0 if server_rates is None else server_rates).to(
+        device="cpu", dtype=torch.float64)
+    if tuple(base.shape) not in ((), (S,), (B, S)) or not bool((base > 0).all()):
+        raise ValueError(f"server_rates: need positive rates, a scalar, ({S},) or ({B}, {S})")
+    rate = base.expand(B, S) / workers.to(torch.float64) if keep_capacity else base.expand(B, S)
+    rate = rate.clamp(*SERVER_RANGE)
+    return (workers.to(device=device, dtype=torch.int32),
+            rate.to(device=device, dtype=torch.float32).contiguous())
