@@ -736,6 +736,54 @@ int lbsim_set_server_workers(lbsim_t* h, const int32_t* workers, int32_t rows, v
 int lbsim_get_server_workers(lbsim_t* h, int32_t* workers_out, void* stream);
 int lbsim_clear_server_workers(lbsim_t* h, void* stream);
 
+/* ---- action latency (per-env control delay applied inside the step) ----
+ * On an enabled handle the weights derived from an action come into force delay_us[b] after the
+ * start of the step they were passed to, 0 <= delay_us <= M * dt (dt = step_interval in us, M =
+ * max_delay_steps).  With m = delay_us / dt, r = delay_us % dt, k = ep_step[b] as the step's
+ * dynamics launch reads it, and W(j) the f32 weight row of the action passed to the step with
+ * ep_step = j of the current episode (W(j < 0) = 1.0 on every server: the warm-up's weights), an
+ * arrival at ta us from the step's start is assigned under W(k - m) if ta >= r and under
+ * W(k - m - 1) if ta < r.  Only the choice reads the weights (SED / SED2 scores, the ALIAS table,
+ * rebuilt at the switch; LSQ / LSQ2 ignore them).  Resets and warm-ups run at 1.0 as before, the
+ * in-launch reset of a next_step_reset handle included (its action is ignored and stored nowhere).
+ * lbsim_action_delay_enable: before the handle's first lbsim_reset (LBSIM_EINVAL after it, and
+ * for max_delay_steps outside [1, 8]; a second call with the same value is a no-op).  Allocates
+ * the weight ring wring[B, max_delay_steps + 2, S] f32 and delay_us[B] (every delay 0; never
+ * moved) and makes the handle a full one whose steps launch dynamics_group_delay_kernel, the full
+ * form with the delay code, in two launches (no other handle's kernels contain that code).  With
+ * every delay 0 results equal a handle that was not enabled.  Composes with every other feature.
+ * lbsim_set_action_delay: delay_s[rows] f32 seconds, a DEVICE pointer, rows = 1 (every env the
+ * same) or B (LBSIM_ESHAPE otherwise); delay_us = (uint32_t)rint((double)delay_s * 1e6).
+ * Validated on the device into a staging copy; the call waits on `stream`, and with any NaN,
+ * negative value or value above M * dt returns LBSIM_EINVAL (the count of offenders in
+ * lbsim_last_error) and leaves what was in force untouched.  The array is rewritten in place: a
+ * step captured into a hipGraph sees later values.  A new delay applies from the next launch on,
+ * the rule evaluated with the current value: shortening a delay can skip an action, lengthening
+ * one can re-apply an older one.  Not part of any snapshot; a shard passes its own rows.
+ * lbsim_get_action_delay: delay_us_out[B] uint32 (DEVICE), asynchronous on `stream`.
+ * lbsim_clear_action_delay: every delay 0, in place, asynchronous on `stream`.
+ * The weight ring is dynamic state that travels BESIDE a snapshot (lbsim_state_size and the
+ * layout of lbsim_get_state are unchanged; lbsim_get_state / lbsim_set_state do not carry it):
+ * lbsim_action_delay_size: the bytes of the ring, B * (max_delay_steps + 2) * S * 4.
+ * lbsim_action_delay_save: the ring rows of the envs with env_mask[b] != 0 (NULL: all) into
+ * dev_buf (DEVICE, [B, max_delay_steps + 2, S] f32), asynchronous on `stream`.
+ * lbsim_action_delay_load: row src_env[b] of dev_buf into env b's rows where 0 <= src_env[b] < B
+ * (any other index: env b keeps its rows; NULL: row b), asynchronous on `stream`.  A wrong
+ * `bytes` is LBSIM_ESHAPE.  Call them beside lbsim_state_save / lbsim_state_load with the same
+ * mask / indices: a restored env replays the same pending actions, a forked env inherits its
+ * source's.
+ * All but enable return LBSIM_EINVAL on a handle that was not enabled.  lbsim_step and
+ * lbsim_reset gain no allocation and no synchronisation. */
+int lbsim_action_delay_enable(lbsim_t* h, int32_t max_delay_steps);
+int lbsim_set_action_delay(lbsim_t* h, const float* delay_s, int32_t rows, void* stream);
+int lbsim_get_action_delay(lbsim_t* h, uint32_t* delay_us_out, void* stream);
+int lbsim_clear_action_delay(lbsim_t* h, void* stream);
+int lbsim_action_delay_size(const lbsim_t* h, size_t* bytes_out);
+int lbsim_action_delay_save(lbsim_t* h, void* dev_buf, size_t bytes, const uint8_t* env_mask,
+                            void* stream);
+int lbsim_action_delay_load(lbsim_t* h, const void* dev_buf, size_t bytes, const int32_t* src_env,
+                            void* stream);
+
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/
  * alias_table.h:82-158, alias_table_build, rebuilt by lb_rl_node.c:92-111 from the weights the

@@ -8,8 +8,8 @@ from .env import (FEATURE_NAMES, DeviceSnapshot, LoadBalanceEnv, LoadBalanceEnvG
                   VecLoadBalanceEnv, make_config)
 from .multi_agent import MultiAgentLoadBalanceEnv, VecMultiAgentLoadBalanceEnv
 from .randomize import (burst_schedule, diurnal_schedule, outage_schedule,
-                        rolling_restart_schedule, sample_cluster_sizes, sample_cross_traffic,
-                        sample_rates, sample_server_workers, schedule_phase)
+                        rolling_restart_schedule, sample_action_delay, sample_cluster_sizes,
+                        sample_cross_traffic, sample_rates, sample_server_workers, schedule_phase)
 from .spaces import Box, MultiDiscrete
 from .workload import (TABLE_BINS, bounded_pareto_table, constant_table, empirical_table,
                        exponential_table, hyperexp_table, lognormal_table, quantile_table,
@@ -22,5 +22,6 @@ __all__ = ["FEATURE_NAMES", "LoadBalanceEnv", "LoadBalanceEnvGym", "VecLoadBalan
            "exponential_table", "bounded_pareto_table", "lognormal_table", "hyperexp_table",
            "weibull_table", "constant_table", "empirical_table", "table_mean", "table_cv2",
            "sample_table_ids", "sample_cluster_sizes", "outage_schedule",
-           "rolling_restart_schedule", "sample_cross_traffic", "sample_server_workers"]
+           "rolling_restart_schedule", "sample_cross_traffic", "sample_server_workers",
+           "sample_action_delay"]
 __version__ = "0.1.0"

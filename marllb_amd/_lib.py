@@ -197,6 +197,13 @@ _SIGNATURES = {
     "lbsim_set_server_workers": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P]),
     "lbsim_get_server_workers": (ctypes.c_int, [_P, _P, _P]),
     "lbsim_clear_server_workers": (ctypes.c_int, [_P, _P]),
+    "lbsim_action_delay_enable": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "lbsim_set_action_delay": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P]),
+    "lbsim_get_action_delay": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_clear_action_delay": (ctypes.c_int, [_P, _P]),
+    "lbsim_action_delay_size": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_size_t)]),
+    "lbsim_action_delay_save": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
+    "lbsim_action_delay_load": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
     "lbsim_server_avail_enable": (ctypes.c_int, [_P]),
     "lbsim_set_server_avail": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_int32, _P]),

@@ -18,6 +18,7 @@
 
 #define LBSIM_CROSS_KERNELS  // cross_convert_kernel is defined in this object (lbsim_cross.h)
 #define LBSIM_WORKERS_KERNELS  // and workers_convert_kernel (lbsim_workers.h)
+#define LBSIM_DELAY_KERNELS  // and delay_convert_kernel / delay_gather_kernel (lbsim_delay.h)
 #include "../../include/lbsim.h"
 #include "lbsim_avail.h"
 #include "lbsim_internal.h"
@@ -124,6 +125,12 @@ struct lbsim {
   // offender count
   void* workers_buf = nullptr;
   ServerWorkers workers{};  // the live array (a null pointer: every server one FIFO pipe)
+  // lbsim_action_delay_enable: one block of 32-bit words, allocated once and never moved -- the
+  // weight ring wring[B, R, S] and the live delay_us[B] the full dynamics kernel reads
+  // (ActionDelay), the delays' staging copy and the offender count
+  void* delay_buf = nullptr;
+  ActionDelay delay{};  // the live arrays (null pointers: actions act at once)
+  int32_t delay_M = 0;  // max_delay_steps
   bool initialised;  // a full reset has been issued
   bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
@@ -1105,7 +1112,7 @@ std::string short_kernel_name(const char* raw) {
 }
 
 LaunchCtx ctx(const lbsim_t* h) {
-  return LaunchCtx{h->plan, h->st, h->prm, h->flow, h->cross, h->workers};
+  return LaunchCtx{h->plan, h->st, h->prm, h->flow, h->cross, h->workers, h->delay};
 }
 
 // The handle's plan: the process's overrides are read on the first call and kept.
@@ -1121,6 +1128,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.work_tables = h->wtab_T > 0;
   in.cross_traffic = h->cross_buf != nullptr;
   in.server_workers = h->workers_buf != nullptr;
+  in.action_delay = h->delay_buf != nullptr;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -1302,6 +1310,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->flow_buf) (void)hipFree(h->flow_buf);
     if (h->cross_buf) (void)hipFree(h->cross_buf);
     if (h->workers_buf) (void)hipFree(h->workers_buf);
+    if (h->delay_buf) (void)hipFree(h->delay_buf);
     if (h->avail_buf) (void)hipFree(h->avail_buf);
     if (h->wtab_buf) (void)hipFree(h->wtab_buf);
     for (hipEvent_t e : h->prof.ev) (void)hipEventDestroy(e);
@@ -2172,6 +2181,136 @@ int lbsim_clear_server_workers(lbsim_t* h, void* stream) {
                      (hipStream_t)stream, (const int32_t*)nullptr, 1, (int64_t)BS, h->S, live,
                      (uint32_t*)(live + 2 * BS));
   return launch_check(h, "workers_convert_kernel");
+}
+
+// ---- action latency (the rule and the kernels: lbsim_delay.h)
+namespace {
+const char kDelayOff[] = "action delay is off: call lbsim_action_delay_enable first";
+size_t delay_ring_words(const lbsim_t* h) {
+  return (size_t)h->B * (size_t)h->delay.R * (size_t)h->S;
+}
+uint32_t* delay_live(lbsim_t* h) { return (uint32_t*)h->delay_buf + delay_ring_words(h); }
+int delay_convert_launch(lbsim_t* h, const float* src, int rows, uint32_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(delay_convert_kernel, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, s,
+                     src, rows, (int32_t)h->B, h->delay_M, (int32_t)h->prm.dt_us, out,
+                     delay_live(h) + 2 * (size_t)h->B);
+  return launch_check(h, "delay_convert_kernel");
+}
+int delay_gather(lbsim_t* h, const char* who, void* dev_buf, size_t bytes, const uint8_t* mask,
+                 const int32_t* src_env, int dir, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->delay_buf == nullptr) return fail(h, LBSIM_EINVAL, "%s", kDelayOff);
+  if (dev_buf == nullptr) return fail(h, LBSIM_EINVAL, "%s: dev_buf is NULL", who);
+  const size_t words = delay_ring_words(h);
+  if (bytes != words * 4)
+    return fail(h, LBSIM_ESHAPE, "%s: the buffer is %zu bytes, need %zu", who, bytes, words * 4);
+  DeviceGuard g(h->device);
+  hipLaunchKernelGGL(delay_gather_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, h->delay.wring, (float*)dev_buf, mask, src_env, dir,
+                     (int32_t)h->B, (int32_t)(h->delay.R * h->S));
+  return launch_check(h, "delay_gather_kernel");
+}
+}  // namespace
+
+int lbsim_action_delay_enable(lbsim_t* h, int32_t max_delay_steps) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!delay_steps_ok(max_delay_steps))
+    return fail(h, LBSIM_EINVAL, "action delay: max_delay_steps must be in [1, %d] (got %d)",
+                (int)kMaxDelaySteps, (int)max_delay_steps);
+  if (h->delay_buf != nullptr) {
+    if (max_delay_steps == h->delay_M) return LBSIM_OK;
+    return fail(h, LBSIM_EINVAL, "action delay is already on with max_delay_steps = %d",
+                (int)h->delay_M);
+  }
+  if (h->reset_seen)
+    return fail(h, LBSIM_EINVAL, "lbsim_action_delay_enable must precede the handle's first "
+                                 "lbsim_reset (it changes which kernels the handle launches)");
+  DeviceGuard g(h->device);
+  const int32_t R = delay_rows(max_delay_steps);
+  const size_t ring = (size_t)h->B * (size_t)R * (size_t)h->S, words = ring + 2 * (size_t)h->B + 1;
+  if (ring > 0x7FFFFFFFu)  // (the gather kernel's row arithmetic and the launch's grid)
+    return fail(h, LBSIM_ENOTSUP, "action delay: a weight ring of %zu words", ring);
+  void* p = nullptr;
+  if (hipMalloc(&p, words * 4) != hipSuccess)
+    return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", words * 4);
+  // a zeroed ring (no row is read before the episode wrote it; a snapshot of it is then defined)
+  // and every delay 0
+  if (hipMemset(p, 0, words * 4) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipFree(p);
+    return fail(h, LBSIM_EDEVICE, "action delay: device init failed");
+  }
+  h->delay_buf = p;
+  h->delay_M = max_delay_steps;
+  h->delay.wring = (float*)p;
+  h->delay.delay_us = (const uint32_t*)p + ring;
+  h->delay.R = R;
+  h->plan = plan_of(h);  // an action-delay handle is a full handle (make_plan)
+  return LBSIM_OK;
+}
+
+int lbsim_set_action_delay(lbsim_t* h, const float* delay_s, int32_t rows, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->delay_buf == nullptr) return fail(h, LBSIM_EINVAL, "%s", kDelayOff);
+  if (delay_s == nullptr) return fail(h, LBSIM_EINVAL, "action delay: delay_s is NULL");
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "action delay: rows must be 1 or num_envs = %d (got %d)", h->B,
+                rows);
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  uint32_t* const live = delay_live(h);
+  uint32_t* const stg = live + h->B;
+  uint32_t* const bad = live + 2 * (size_t)h->B;
+  if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "action delay: hipMemsetAsync failed");
+  const int rc = delay_convert_launch(h, delay_s, (int)rows, stg, s);
+  if (rc != LBSIM_OK) return rc;
+  uint32_t nbad = 0;
+  if (hipMemcpyAsync(&nbad, bad, sizeof(nbad), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "action delay: conversion failed");
+  if (nbad != 0u)  // the live array is untouched: the previous delays stay in force
+    return fail(h, LBSIM_EINVAL, "action delay: %u delay(s) NaN, negative or above "
+                                 "max_delay_steps * step_interval = %u us", nbad,
+                delay_max_us(h->delay_M, h->prm.dt_us));
+  if (hipMemcpyAsync(live, stg, (size_t)h->B * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "action delay: device copy failed");
+  return LBSIM_OK;
+}
+
+int lbsim_get_action_delay(lbsim_t* h, uint32_t* delay_us_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->delay_buf == nullptr) return fail(h, LBSIM_EINVAL, "%s", kDelayOff);
+  if (delay_us_out == nullptr) return fail(h, LBSIM_EINVAL, "action delay: delay_us_out is NULL");
+  DeviceGuard g(h->device);
+  if (hipMemcpyAsync(delay_us_out, h->delay.delay_us, (size_t)h->B * 4, hipMemcpyDeviceToDevice,
+                     (hipStream_t)stream) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "action delay: device copy failed");
+  return LBSIM_OK;
+}
+
+int lbsim_clear_action_delay(lbsim_t* h, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->delay_buf == nullptr) return fail(h, LBSIM_EINVAL, "%s", kDelayOff);
+  DeviceGuard g(h->device);
+  return delay_convert_launch(h, nullptr, 1, delay_live(h), (hipStream_t)stream);
+}
+
+int lbsim_action_delay_size(const lbsim_t* h, size_t* bytes_out) {
+  if (h == nullptr || bytes_out == nullptr) return LBSIM_EINVAL;
+  if (h->delay_buf == nullptr) return fail(const_cast<lbsim_t*>(h), LBSIM_EINVAL, "%s", kDelayOff);
+  *bytes_out = delay_ring_words(h) * 4;
+  return LBSIM_OK;
+}
+
+int lbsim_action_delay_save(lbsim_t* h, void* dev_buf, size_t bytes, const uint8_t* env_mask,
+                            void* stream) {
+  return delay_gather(h, "lbsim_action_delay_save", dev_buf, bytes, env_mask, nullptr, 0, stream);
+}
+
+int lbsim_action_delay_load(lbsim_t* h, const void* dev_buf, size_t bytes, const int32_t* src_env,
+                            void* stream) {
+  return delay_gather(h, "lbsim_action_delay_load", const_cast<void*>(dev_buf), bytes, nullptr,
+                      src_env, 1, stream);
 }
 
 int lbsim_server_avail_enable(lbsim_t* h) {

@@ -42,6 +42,14 @@ void launch_dynamics_t(const LaunchCtx& L, const void* action, int dtype, int32_
     }); });
     return;
   }
+#if LBSIM_DYN_MODE != 1
+  // a step of an action-delay handle (a full one): its own kernels, in their own objects
+  if (d.full && L.delay.wring != nullptr) {
+    if (MODE == kModeStep) launch_dynamics_delay_step(L, action, dtype, assign, mask, stream);
+    else launch_dynamics_delay_step_nr(L, action, dtype, assign, mask, stream);
+    return;
+  }
+#endif
   // server per lane: G lanes per env (32 / 64 for S > 16), epw <= 64 / G envs per wave, which
   // only this kernel's own copy of the parameters carries
   SimParams prm = L.prm;

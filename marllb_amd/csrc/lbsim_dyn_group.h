@@ -27,6 +27,7 @@
 #pragma once
 
 #include "lbsim_cross.h"
+#include "lbsim_delay.h"
 #include "lbsim_kernels.h"
 #include "lbsim_workers.h"
 
@@ -167,6 +168,17 @@ struct CrossLane {
 struct WorkLane {
   bool on = false;
   int32_t c = 1;
+};
+
+// Action latency (lbsim_delay.h) as a lane of dynamics_group_delay_kernel sees
+// it (the DELAY instantiations alone).  pend: the step's arrivals from ta = r on are assigned under
+// another weight row than the one the step starts on (the same in every lane of a group; false
+// with r = 0, in a warm-up step and in a resetting group); w2: this lane's own server's word of
+// that row (1.0 in a lane without a server).
+struct DelayLane {
+  bool pend = false;
+  int32_t r = 0;
+  float w2 = 1.0f;
 };
 
 // The lane's queue by position from the head (lbsim_workers.h's accessor): the LDS window below
@@ -334,7 +346,7 @@ __device__ __forceinline__ GroupConst group_const(const SimParams& p, float mean
 // VPP, exact flow statistics (fs_on), workload tables (ws) -- compiled only into
 // dynamics_group_full_kernel, so none of their registers weigh on the plain kernel (126 VGPRs, 4
 // waves per SIMD; with them inlined it took 164).
-template <int G, int POLICY, bool TRACE, bool FAST, bool FULL = false>
+template <int G, int POLICY, bool TRACE, bool FAST, bool FULL = false, bool DELAY = false>
 __device__ __forceinline__ void group_event_loop(const DevState& st, const SimParams& p,
                                                  LaneState<1>& E, SrvLane& V, int s, int gbase,
                                                  int n_alias, const GroupConst& gc, int2* win,
@@ -343,7 +355,8 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
                                                  const TraceSel& ts = TraceSel{},
                                                  const WorkSel& ws = WorkSel{},
                                                  const CrossLane& cx = CrossLane{},
-                                                 const WorkLane& wk = WorkLane{}) {
+                                                 const WorkLane& wk = WorkLane{},
+                                                 DelayLane dl = DelayLane{}) {
   constexpr int WL = kGroupWL;
   constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
   constexpr bool alias = POLICY == kPolicyAlias;
@@ -368,6 +381,24 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
   uint32_t kbase = E.arr_idx + 1u, rbase = 0u;
   if constexpr (TRACE) rbase = trace_row_in(ts.rows, E.gid, E.episode, kbase);
   for (;;) {
+    if constexpr (DELAY && !lsq) {
+      // action latency (§3.19): from the first arrival at or after r on, the second row -- once
+      // per step, the same in every lane of the group; possibly an iteration or two ahead of the
+      // arrival itself: nothing is chosen before it
+      if (dl.pend && E.next_arr >= dl.r) {
+        dl.pend = false;
+        if constexpr (alias) {
+          // the table again, by the same code, over the second row where it is: one word in each
+          // lane of the group (every lane of the group runs the same build, so the lanes it reads
+          // are active)
+          const float w2 = dl.w2;
+          n_alias = build_alias_fn<G>([&](int k) { return __shfl(w2, gbase + k, 64); }, S, tab);
+        } else if (V.act) {
+          V.den = (double)dl.w2 + 1e-9;
+          V.rcp = 1.0 / V.den;
+        }
+      }
+    }
     if ((it & (uint32_t)(G - 1)) == 0u) {
       cbase = E.arr_idx + 1u;
       const uint32_t k = cbase + (uint32_t)s;
@@ -609,7 +640,7 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
   }
 }
 
-template <int G, int POLICY, bool TRACE, bool FULL = false>
+template <int G, int POLICY, bool TRACE, bool FULL = false, bool DELAY = false>
 __device__ __forceinline__ void sim_step_group(const DevState& st, const SimParams& p,
                                                LaneState<1>& E, SrvLane& V, uint32_t b, int s,
                                                int gbase, float w_own, const float (&wall)[G],
@@ -617,7 +648,8 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                                                bool fs_on = false,
                                                const TraceSel& ts = TraceSel{},
                                                const CrossLane& cx = CrossLane{},
-                                               const WorkLane& wk = WorkLane{}) {
+                                               const WorkLane& wk = WorkLane{},
+                                               const DelayLane& dl = DelayLane{}) {
   constexpr int WL = kGroupWL;
   const int S = p.S, Q = p.Q;
   const int32_t dt = p.dt_us;
@@ -747,9 +779,9 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
   const bool finite = lsq || alias || !V.act ||
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
-    group_event_loop<G, POLICY, TRACE, false, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                                    acache, my_res, my_ring, fs_on, ts, ws, cx,
-                                                    wk);
+    group_event_loop<G, POLICY, TRACE, false, true, DELAY>(st, p, E, V, s, gbase, n_alias, gc, win,
+                                                           atab, acache, my_res, my_ring, fs_on,
+                                                           ts, ws, cx, wk, dl);
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
   } else if (__all(finite)) {
@@ -800,14 +832,15 @@ struct DynGroupLds {
 // One step (or reset) of the 64 / G envs of wave `wave` (env b = wave * 64 / G + lane / G), lane s
 // of a group owning server s: state in, the event loop, state back to HBM.  Lanes of envs past B
 // (or outside the reset mask) return at once, whole groups together.
-template <int G, int MODE, int POLICY, bool TRACE, bool FULL = false>
+template <int G, int MODE, int POLICY, bool TRACE, bool FULL = false, bool DELAY = false>
 __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimParams& p,
                                                const void* action, int action_dtype,
                                                int32_t* assign_out, const uint8_t* reset_mask,
                                                uint32_t wave, int lane, DynGroupLds<POLICY>& L,
                                                const FlowStats& fs = FlowStats{},
                                                const CrossTraffic& ct = CrossTraffic{},
-                                               const ServerWorkers& sw = ServerWorkers{}) {
+                                               const ServerWorkers& sw = ServerWorkers{},
+                                               const ActionDelay& ad = ActionDelay{}) {
   static_assert(G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64,
                 "group = a power of two lanes of the wave");
   constexpr int WL = kGroupWL;
@@ -1010,11 +1043,39 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
       if (cx.on) cx.salt = cross_salt(p.key0, p.key1, E.gid, E.episode);
     }
   };
+  DelayLane dl;  // action latency: off in a reset's warm-up and in a resetting group
+  auto delay_in = [&]() {  // after load_in: the rows this step runs under instead of its action's
+    if constexpr (DELAY) {
+      const int32_t k = st.ep_step[b];
+      const uint32_t d = ad.delay_us[b];
+      const int32_t m = delay_whole(d, p.dt_us), r = delay_rem(d, p.dt_us);
+      // lane s reads and writes its own server's word of the env's rows: coalesced
+      float* const rows = ad.wring + (size_t)b * (size_t)(ad.R * S) + (size_t)(V.act ? s : 0);
+      const float own = w_own;  // W(k): the launch's own action (1.0 in a lane past S)
+      auto word = [&](int32_t j) -> float {
+        if (delay_is_ones(j) || !V.act) return 1.0f;
+        if (j == k) return own;  // m = 0: not through memory
+        return rows[delay_row(j, ad.R) * S];
+      };
+      const float w_new = word(delay_step_new(k, m));
+      const float w_old = word(delay_step_old(k, m));
+      if (V.act && k >= 0) rows[delay_row(k, ad.R) * S] = own;  // a row this launch does not read
+      dl.r = r;
+      dl.pend = r != 0;
+      dl.w2 = w_new;
+      w_own = r != 0 ? w_old : w_new;  // in force at ta = 0
+      if constexpr (alias) {
+#pragma unroll
+        for (int j = 0; j < G; ++j) wall[j] = __shfl(w_own, gbase + j, 64);
+      }
+    }
+  };
   if constexpr (MODE == kModeStep) {
     load_in();
     cross_in();
-    sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w_own, wall, win, atab,
-                                           acache, fs_on, ts, cx, wk);
+    delay_in();
+    sim_step_group<G, POLICY, TRACE, FULL, DELAY>(st, p, E, V, b, s, gbase, w_own, wall, win,
+                                                  atab, acache, fs_on, ts, cx, wk, dl);
   } else if constexpr (MODE == kModeReset) {
     reset_in();
     cross_in();
@@ -1033,11 +1094,14 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     if (rs) reset_in();
     else load_in();
     cross_in();
+    if constexpr (DELAY) {
+      if (!rs) delay_in();  // (a resetting step stores no row: its action is ignored)
+    }
     const int nsteps = rs ? p.warmup_steps : 1;
     const float w = rs ? 1.0f : w_own;
     for (int k = 0; k < nsteps; ++k)
-      sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, w, wall, win, atab,
-                                             acache, fs_on, ts, cx, wk);
+      sim_step_group<G, POLICY, TRACE, FULL, DELAY>(st, p, E, V, b, s, gbase, w, wall, win, atab,
+                                                    acache, fs_on, ts, cx, wk, dl);
     if (rs) reset_out(-1);
   }
 
@@ -1116,6 +1180,23 @@ __global__ void __launch_bounds__(64)
   dyn_group_wave<G, MODE, POLICY, TRACE, true>(st, p, action, action_dtype, assign_out,
                                                reset_mask, blockIdx.x, (int)threadIdx.x, L, fs, ct,
                                                sw);
+}
+
+// The full form with action latency (ad: the weight ring and the delays,
+// lbsim_delay.h), for the steps of an enabled handle (its resets run the kernel above: a reset
+// and its warm-up have no delay).  Instantiations of their own (lbsim_dyn_delay.hip): compiled
+// into the full kernel behind a run-time test, the code took the full SED kernels from 166 to 172
+// VGPRs, from 3 waves per SIMD to 2, for every full handle whether it had a delay or not.
+template <int G, int MODE, int POLICY, bool TRACE>
+__global__ void __launch_bounds__(64)
+    dynamics_group_delay_kernel(DevState st, SimParams p, const void* action, int action_dtype,
+                                int32_t* assign_out, const uint8_t* reset_mask, FlowStats fs,
+                                CrossTraffic ct, ServerWorkers sw, ActionDelay ad) {
+  static_assert(MODE != kModeReset, "a reset has no delay");
+  __shared__ DynGroupLds<POLICY> L;
+  dyn_group_wave<G, MODE, POLICY, TRACE, true, true>(st, p, action, action_dtype, assign_out,
+                                                     reset_mask, blockIdx.x, (int)threadIdx.x, L,
+                                                     fs, ct, sw, ad);
 }
 
 }  // namespace lbk

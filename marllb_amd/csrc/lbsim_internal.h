@@ -3,8 +3,11 @@
 //
 //   lbsim_cross.h      hidden cross traffic: the host / device rule and its conversion kernel
 //   lbsim_workers.h    multi-worker servers: the host / device rule and its conversion kernel
+//   lbsim_delay.h      action latency: the host / device rule, its conversion and gather kernels
 //   lbsim_plan.h       make_plan: which kernels a handle's step and reset launch, decided once
 //                      (host-only; the launchers below turn the plan into template arguments)
+//   lbsim_dyn_delay.hip  dynamics_group_delay_kernel launchers (action latency); built twice
+//                      (-DLBSIM_DYN_MODE=0 step, 2 step_nr)
 //   lbsim_dyn.hip      dynamics_kernel / dynamics_group_kernel launchers; built three times
 //                      (-DLBSIM_DYN_MODE=0: step, 1: reset, 2: the next-step auto-reset step)
 //   lbsim_obs.hip      observe_kernel launchers
@@ -21,6 +24,7 @@
 
 #include "../../include/lbsim.h"
 #include "lbsim_cross.h"
+#include "lbsim_delay.h"
 #include "lbsim_kernels.h"
 #include "lbsim_plan.h"
 #include "lbsim_workers.h"
@@ -54,6 +58,7 @@ struct LaunchCtx {
   const FlowStats& flow;  // the full group dynamics' flow statistics (null pointers: off)
   const CrossTraffic& cross;  // and its cross traffic (lbsim_cross.h; null pointers: none)
   const ServerWorkers& workers;  // and its servers' worker counts (lbsim_workers.h; null: none)
+  const ActionDelay& delay;  // and its action latency's arrays (lbsim_delay.h; null: none)
 };
 
 // Runtime value -> template argument: pick<2, 4, 8>(v, f) calls f(std::integral_constant<int, v>)
@@ -79,6 +84,12 @@ void launch_dynamics_reset(const LaunchCtx& L, const void* action, int dtype, in
 // The step of a next-step auto-reset handle (kModeStepNR): envs done last step reset instead.
 void launch_dynamics_step_nr(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
                              const uint8_t* mask, hipStream_t s);
+// The same two for a handle with action latency (lbsim_dyn_delay.hip: dynamics_group_delay_kernel;
+// the plan is a full group one and L.delay holds the arrays).
+void launch_dynamics_delay_step(const LaunchCtx& L, const void* action, int dtype,
+                                int32_t* assign, const uint8_t* mask, hipStream_t s);
+void launch_dynamics_delay_step_nr(const LaunchCtx& L, const void* action, int dtype,
+                                   int32_t* assign, const uint8_t* mask, hipStream_t s);
 
 void launch_observe_step(const LaunchCtx& L, const ObsOutputs& o, const uint8_t* mask,
                          hipStream_t s);

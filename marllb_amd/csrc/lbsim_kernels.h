@@ -518,21 +518,26 @@ __device__ __forceinline__ T sel(const T (&a)[MAXS], int i) {
 // fields: F_TAB0 = odd (f32 bits, the alias_t float), F_TAB1 = alias | server << 8.
 // `tab(f, k)` is the table word f (0: odd, 1: alias | server << 8) of active position k.
 // Returns the active count.
-template <int MAXS, typename Tab>
-__device__ int build_alias(const float (&w)[MAXS], int S, Tab tab) {
+// `w(s)` is the weight of server s: the row may live in a register array (build_alias below) or
+// in the lanes of a group (action latency's rebuild at the switch, lbsim_dyn_group.h).
+template <int MAXS, typename WF, typename Tab>
+__device__ int build_alias_fn(WF w, int S, Tab tab) {
   int n = 0;
   double sum = 0.0;
 #pragma unroll
   for (int s = 0; s < MAXS; ++s) {
-    if (s < S && w[s] > 0.0f) {
-      tab(0, n) = (int32_t)0x3f800000;  // (1, 0)
-      tab(1, n) = s << 8;
-      sum += (double)w[s];
-      ++n;
+    if (s < S) {
+      const float ws = w(s);
+      if (ws > 0.0f) {
+        tab(0, n) = (int32_t)0x3f800000;  // (1, 0)
+        tab(1, n) = s << 8;
+        sum += (double)ws;
+        ++n;
+      }
     }
   }
   const double avg = sum / ((double)n + 1e-6);
-  auto wk = [&](int k) { return (double)sel<MAXS>(w, tab(1, k) >> 8); };
+  auto wk = [&](int k) { return (double)w(tab(1, k) >> 8); };
   int si = 0, bi = 0, sk = -1, bk = -1;
   double sp = 0.0, bp = 0.0;
   auto next_small = [&]() {
@@ -552,6 +557,10 @@ __device__ int build_alias(const float (&w)[MAXS], int S, Tab tab) {
     if (bp < 1.0) { sk = bk; sp = bp; next_big(); } else { next_small(); }
   }
   return n;
+}
+template <int MAXS, typename Tab>
+__device__ int build_alias(const float (&w)[MAXS], int S, Tab tab) {
+  return build_alias_fn<MAXS>([&](int s) { return sel<MAXS>(w, s); }, S, tab);
 }
 
 // ALIAS pick for an arrival with hash word u: rand_num = U * n (U = 24 bits of u, in [0, 1)),

@@ -43,7 +43,7 @@ struct Overrides {
 };
 
 // What the plan depends on: fixed when the handle is created, but for flow_stats,
-// cross_traffic and server_workers (set before the first reset) and work_tables (the plan is made again when tables
+// cross_traffic, server_workers and action_delay (set before the first reset) and work_tables (the plan is made again when tables
 // come into force or are cleared).
 struct PlanInput {
   int B, S, Q;
@@ -62,6 +62,7 @@ struct PlanInput {
   bool work_tables;  // workload tables are in force (lbsim_set_workload_tables)
   bool cross_traffic = false;  // hidden cross traffic is on (lbsim_cross_traffic_enable)
   bool server_workers = false;  // multi-worker servers are on (lbsim_server_workers_enable)
+  bool action_delay = false;  // action latency is on (lbsim_action_delay_enable)
 };
 
 enum StepForm { kStepWave, kStepGroupFused, kStepTwoLaunch };
@@ -121,8 +122,9 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
   // shared instantiations moved the headline kernel's registers).
   // Cross traffic: the hidden flows' decision, flag and count are compiled into the full form alone.
   // Multi-worker servers: so are the start rule and the sorted insert.
+  // Action latency: so are the weight ring and the mid-step switch.
   const bool full_only = in.res_vpp || in.flow_stats || in.work_tables || in.cross_traffic ||
-                         in.server_workers;
+                         in.server_workers || in.action_delay;
   const bool wave_fits = ov.dyn_wave != 0 && !ov.group_lanes_set &&
                          in.dyn_mapping != LBSIM_DYN_ENV_PER_LANE && S <= 8 && in.Q <= 32 &&
                          in.policy != LBSIM_POLICY_ALIAS && !in.fail && !in.leak && !in.split &&

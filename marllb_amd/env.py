@@ -515,6 +515,55 @@ class Handle:
         """Every count 1 (lbsim_clear_server_workers), on the current stream."""
         self.check(self.lib.lbsim_clear_server_workers(self.h, ctypes.c_void_p(self._stream())))
 
+    def enable_action_delay(self, max_delay_steps: int = 1) -> None:
+        """Action latency from now on (lbsim_action_delay_enable): before the handle's first
+        reset, max_delay_steps in [1, 8] (ValueError otherwise)."""
+        self.check(self.lib.lbsim_action_delay_enable(self.h, int(max_delay_steps)))
+
+    def set_action_delay(self, delay_s, *, rows: int) -> None:
+        """Delays (lbsim_set_action_delay): delay_s (rows,) float32 seconds contiguous on the
+        handle's device, rows = 1 or B."""
+        self.check(self.lib.lbsim_set_action_delay(
+            self.h, ctypes.c_void_p(delay_s.data_ptr()), int(rows),
+            ctypes.c_void_p(self._stream())))
+
+    def action_delay_us(self):
+        """(B,) int32 device tensor holding the uint32 delays in force, in us
+        (lbsim_get_action_delay)."""
+        torch = _torch()
+        out = torch.empty(int(self.cfg.num_envs), dtype=torch.int32,
+                          device=torch.device("cuda", self.device_index))
+        self.check(self.lib.lbsim_get_action_delay(self.h, ctypes.c_void_p(out.data_ptr()),
+                                                   ctypes.c_void_p(self._stream())))
+        return out
+
+    def clear_action_delay(self) -> None:
+        """Every delay 0 (lbsim_clear_action_delay), on the current stream."""
+        self.check(self.lib.lbsim_clear_action_delay(self.h, ctypes.c_void_p(self._stream())))
+
+    def action_delay_size(self) -> int:
+        """Bytes of the weight ring, the buffer of action_delay_save / _load."""
+        n = ctypes.c_size_t()
+        self.check(self.lib.lbsim_action_delay_size(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def action_delay_save(self, buf, mask=None) -> None:
+        """The weight-ring rows of the envs with mask[b] set (uint8 device tensor; None: every
+        env) into buf, a contiguous device tensor of action_delay_size() bytes laid out
+        (B, max_delay_steps + 2, S) float32; one kernel on the current stream."""
+        self.check(self.lib.lbsim_action_delay_save(
+            self.h, ctypes.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size(),
+            ctypes.c_void_p(mask.data_ptr() if mask is not None else None),
+            ctypes.c_void_p(self._stream())))
+
+    def action_delay_load(self, buf, src=None) -> None:
+        """Env b takes the rows buf holds for env src[b] (int32 device tensor; None: its own; an
+        entry outside [0, B) keeps env b's); one kernel on the current stream."""
+        self.check(self.lib.lbsim_action_delay_load(
+            self.h, ctypes.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size(),
+            ctypes.c_void_p(src.data_ptr() if src is not None else None),
+            ctypes.c_void_p(self._stream())))
+
     def enable_server_avail(self) -> None:
         """Scripted server availability from now on (lbsim_server_avail_enable): before the
         handle's first reset (ValueError after it); LbsimError ENOTSUP with fail_prob > 0."""
@@ -563,14 +612,17 @@ class DeviceSnapshot:
     obs     (B, S, 11) f32: the observation batch the env had returned last
     up_ret  (B,) f64 episode returns of feature_mode="upstream" (None otherwise)
     host    the single-env facade's own bookkeeping (LoadBalanceEnv.snapshot), else None
-    Not saved, as for get_state(): the seed, per-env rates and rate schedules, the flow statistics
-    and the trace.
+    delay   (B, max_delay_steps + 2, S) f32: the pending actions' weight rows of an action_delay
+            env, else None.  get_state() does not hold them.
+    Not saved, as for get_state(): the seed, per-env rates and rate schedules, the flow statistics,
+    the trace and the action delays themselves (they stay with the slot, like the rates).
     """
 
-    __slots__ = ("state", "obs", "up_ret", "host")
+    __slots__ = ("state", "obs", "up_ret", "host", "delay")
 
-    def __init__(self, state, obs, up_ret=None, host=None):
+    def __init__(self, state, obs, up_ret=None, host=None, delay=None):
         self.state, self.obs, self.up_ret, self.host = state, obs, up_ret, host
+        self.delay = delay
 
 
 class VecLoadBalanceEnv:
@@ -612,6 +664,12 @@ class VecLoadBalanceEnv:
     queue, so flows are served side by side and a short one overtakes a long one (DESIGN.md
     §3.18); not with lost_fin_prob > 0 or duration_mode="service" (LbsimError, code ENOTSUP).
     Such an env steps through the full server-per-lane dynamics kernel too.
+    action_delay=True lets set_action_delay give each env a control delay (seconds, a scalar or
+    (B,) array: enabled, and those delays set), at most max_delay_steps (1 to 8) step intervals:
+    the weights of an action come into force that long after the start of the step they were
+    passed to, inside the step where the delay is no whole number of intervals, and until then
+    the previous actions' weights (1.0 before the episode's first) keep routing flows (DESIGN.md
+    §3.19).  Composes with every other option; a full-kernel env as well.
     """
 
     def __init__(self, num_envs: int, num_servers: int = 4, *, device=None,
@@ -619,7 +677,8 @@ class VecLoadBalanceEnv:
                  strict_actions: bool = False, feature_mode: str = "problem01",
                  graph_mode: bool = False, autoreset_mode: str = "same_step",
                  flow_stats: bool = False, server_availability: bool = False,
-                 cross_traffic: bool = False, server_workers=False, **kwargs):
+                 cross_traffic: bool = False, server_workers=False, action_delay=False,
+                 max_delay_steps: int = 1, **kwargs):
         torch = _torch()
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError(f"Unknown autoreset_mode: {autoreset_mode}")
@@ -664,6 +723,12 @@ class VecLoadBalanceEnv:
             self.handle.enable_server_workers()
             if server_workers is not True:
                 self.set_server_workers(server_workers)
+        self.action_delay = action_delay is not False and action_delay is not None
+        self.max_delay_steps = int(max_delay_steps)
+        if self.action_delay:
+            self.handle.enable_action_delay(max_delay_steps)
+            if action_delay is not True:
+                self.set_action_delay(action_delay)
         if self.trace is not None:
             if _is_bank(self.trace):
                 self.handle.set_trace_bank(self.trace)
@@ -985,6 +1050,37 @@ class VecLoadBalanceEnv:
     def clear_server_workers(self) -> None:
         """Every server back to one worker."""
         self.handle.clear_server_workers()
+
+    # ---- action latency (action_delay=True; DESIGN.md §3.19)
+    def set_action_delay(self, seconds) -> None:
+        """Per-env control delay: seconds, a scalar or (B,) floats in [0, max_delay_steps *
+        step_interval], a tensor or array on any device; rounded to whole us.  From the next
+        launch on, the weights in force at time t of a step are those of the action given delay
+        seconds before (1.0 before the episode's first action; resets and warm-ups run at 1.0).
+        The rule is evaluated with the current value: shortening a delay can skip an action,
+        lengthening one can apply an older one again.  NaN, a negative value or one above the
+        maximum: ValueError, the previous delays stay in force.  Not part of get_state() or of a
+        snapshot; a shard passes its own rows.  graph_mode: calls rewrite the same device array,
+        so replays see them."""
+        torch = _torch()
+        B = self.num_envs
+        d = torch.as_tensor(seconds)
+        if tuple(d.shape) not in ((), (1,), (B,)):
+            raise ValueError(f"seconds: expected a scalar or shape ({B},), got {tuple(d.shape)}")
+        if d.dtype == torch.bool:
+            raise ValueError("seconds: expected numbers")
+        d = d.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        self.handle.set_action_delay(d, rows=B if d.numel() == B else 1)
+
+    def get_action_delay(self):
+        """(B,) f32 device tensor: the delays in force, in seconds."""
+        torch = _torch()
+        us = self.handle.action_delay_us().to(torch.int64) & 0xFFFFFFFF
+        return (us.to(torch.float64) * 1e-6).to(torch.float32)
+
+    def clear_action_delay(self) -> None:
+        """Every delay 0: actions act at once again."""
+        self.handle.clear_action_delay()
 
     @property
     def rates(self):
@@ -1312,8 +1408,15 @@ class VecLoadBalanceEnv:
                 torch.empty(self.handle.state_size(), dtype=torch.uint8, device=self.device),
                 torch.empty_like(self._last_obs),
                 torch.zeros(B, dtype=torch.float64, device=self.device) if upstream else None)
+            if self.action_delay:  # the pending actions' weight rows travel beside the state
+                out.delay = torch.empty((B, self.max_delay_steps + 2, self.num_servers),
+                                        dtype=torch.float32, device=self.device)
         m = None if mask is None else self._mask(mask)
         self.handle.state_save(out.state, m)
+        if self.action_delay:
+            if out.delay is None:
+                raise ValueError("snapshot(out=...): out was not taken from an action_delay env")
+            self.handle.action_delay_save(out.delay, m)
         ret = None
         if upstream:
             ret = self._up_ret if self._up_ret is not None else torch.zeros_like(out.up_ret)
@@ -1350,8 +1453,12 @@ class VecLoadBalanceEnv:
         upstream = self.feature_mode == "upstream"
         if upstream and self._up_ret is None:
             self._up_ret = torch.zeros(B, dtype=torch.float64, device=self.device)
+        if self.action_delay and snap.delay is None:
+            raise ValueError("restore(): the snapshot was not taken from an action_delay env")
         if mask is None and src is None:
             self.handle.state_load(snap.state)
+            if self.action_delay:
+                self.handle.action_delay_load(snap.delay)
             obs = self._obs_buffer()
             obs.copy_(snap.obs)
             if upstream:
@@ -1375,6 +1482,8 @@ class VecLoadBalanceEnv:
             ibuf = self._buf("restore_src", (B,), torch.int32)
             ibuf.copy_(idx)
             self.handle.state_load(snap.state, ibuf)
+            if self.action_delay:
+                self.handle.action_delay_load(snap.delay, ibuf)
             ok = (ibuf >= 0) & (ibuf < B)
             rows = ibuf.clamp(0, B - 1).long()
             new = torch.where(ok.view(B, 1, 1), snap.obs.index_select(0, rows), self._last_obs)
@@ -1790,6 +1899,22 @@ class LoadBalanceEnv:
 
     def clear_server_workers(self) -> None:
         self._workers_vec().clear_server_workers()
+
+    # ---- action latency (LoadBalanceEnv(action_delay=0.02 or True))
+    def _delay_vec(self) -> "VecLoadBalanceEnv":
+        if self._vec is None:
+            raise RuntimeError("action delay needs the GPU simulator (not reference_plumbing)")
+        return self._vec
+
+    def set_action_delay(self, seconds: float) -> None:
+        """The env's control delay in seconds (VecLoadBalanceEnv.set_action_delay)."""
+        self._delay_vec().set_action_delay(float(seconds))
+
+    def get_action_delay(self) -> float:
+        return float(self._delay_vec().get_action_delay()[0].item())
+
+    def clear_action_delay(self) -> None:
+        self._delay_vec().clear_action_delay()
 
     # ---- workload tables (VecLoadBalanceEnv.set_workload_tables of the one env)
     def _work_vec(self) -> "VecLoadBalanceEnv":

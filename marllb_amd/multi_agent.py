@@ -109,6 +109,17 @@ class MultiAgentLoadBalanceEnv:
                    self.env.current_step / self.env.max_steps, self.num_agents]
         return np.concatenate([np.zeros(self.total_servers * 4), metrics])
 
+    def set_action_delay(self, seconds: float) -> None:
+        """The env's control delay in seconds: LoadBalanceEnv.set_action_delay (an env made with
+        action_delay=True or a delay); every agent's weights are delayed alike."""
+        self.env.set_action_delay(seconds)
+
+    def get_action_delay(self) -> float:
+        return self.env.get_action_delay()
+
+    def clear_action_delay(self) -> None:
+        self.env.clear_action_delay()
+
     def render(self, mode: str = "human"):
         return self.env.render(mode)
 
@@ -251,6 +262,17 @@ class VecMultiAgentLoadBalanceEnv:
 
     def clear_server_workers(self) -> None:
         self.vec.clear_server_workers()
+
+    def set_action_delay(self, seconds) -> None:
+        """Per-env control delay in seconds, a scalar or (B,): VecLoadBalanceEnv.set_action_delay
+        (an env made with action_delay=True); every agent's weights are delayed alike."""
+        self.vec.set_action_delay(seconds)
+
+    def get_action_delay(self):
+        return self.vec.get_action_delay()
+
+    def clear_action_delay(self) -> None:
+        self.vec.clear_action_delay()
 
     def clear_cross_traffic(self) -> None:
         self.vec.clear_cross_traffic()

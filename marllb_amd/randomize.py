@@ -297,3 +297,30 @@ def sample_server_workers(num_envs: int, num_servers: int, choices=(1, 2, 4), se
     rate = rate.clamp(*SERVER_RANGE)
     return (workers.to(device=device, dtype=torch.int32),
             rate.to(device=device, dtype=torch.float32).contiguous())
+
+
+# ---- action latency (VecLoadBalanceEnv.set_action_delay)
+
+
+def sample_action_delay(num_envs: int, low: float = 0.0, high: float = 0.25, seed: int = 0, *,
+                        max_delay: float | None = None, device=None):
+    """-> (B,) float32 seconds for VecLoadBalanceEnv.set_action_delay: each env's control delay,
+    uniform over [low, high], clamped to the valid range [0, max_delay] (max_delay: the env's
+    max_delay_steps * step_interval; default `high`).  Deterministic for a seed."""
+    import torch
+
+    B = int(num_envs)
+    if B < 1:
+        raise ValueError(f"need num_envs >= 1 (got {num_envs})")
+    lo, hi = float(low), float(high)
+    if not (0.0 <= lo <= hi) or hi != hi or hi == float("inf"):
+        raise ValueError(f"need 0 <= low <= high, finite (got {low}, {high})")
+    top = hi if max_delay is None else float(max_delay)
+    if not top >= 0.0:
+        raise ValueError(f"max_delay: need a value >= 0 (got {max_delay})")
+    g = torch.Generator().manual_seed(int(seed))
+    u = torch.rand(B, generator=g, dtype=torch.float64)
+    # (clamped in f64: the f32 of the bound is within half an ulp of it, far below the half
+    # microsecond that the conversion to whole us rounds away)
+    d = (lo + (hi - lo) * u).clamp(0.0, top)
+    return d.to(device=device, dtype=torch.float32).contiguous()
