@@ -736,6 +736,35 @@ int lbsim_set_server_workers(lbsim_t* h, const int32_t* workers, int32_t rows, v
 int lbsim_get_server_workers(lbsim_t* h, int32_t* workers_out, void* stream);
 int lbsim_clear_server_workers(lbsim_t* h, void* stream);
 
+/* ---- ground-truth server state (for a centralised critic or mixer) ----
+ * What the simulator knows about each server between two launches and the observation does not
+ * show, one row of LBSIM_TRUTH_COLS f32 per (env, server).  With n the flows in the server's
+ * queue (in service included), c its worker count (1 without server workers) and q(pos) the
+ * completion time, in us from the start of the next step, of the queued flow at position pos in
+ * completion order:
+ *   0 n_total    (float)n
+ *   1 n_hidden   hidden cross-traffic flows among them; 0 on a handle without cross traffic
+ *   2 busy       (float)min(n, c)
+ *   3 cpu        busy / (float)c
+ *   4 wait_s     n < c ? 0 : max(0, q(n - c)): until a worker is free for a flow arriving now
+ *   5 backlog_s  n == 0 ? 0 : max(0, q(n - 1)): until the server drains with no further arrival
+ *   6 up         0 while the server is down (random failures or scripted availability: the
+ *                up_now of lbsim_get_server_avail), else 1
+ *   7 capacity   (float)c * mu, mu the server rate lbsim_get_env_rates reports: that of the env's
+ *                next step, rate schedules included
+ * Times are (float)us * 1e-6f seconds.  Every value is >= 0, and each is an exact conversion or
+ * one correctly rounded f32 operation.  The rows describe the state as it stands: after a
+ * lbsim_reset of done envs, the new episode.  Utilisation averaged over a step is not included.
+ * lbsim_ground_truth: truth_out[B, S, LBSIM_TRUTH_COLS] f32, a DEVICE pointer aligned to 16
+ * bytes; one small kernel on `stream` that reads the state and writes truth_out only: no
+ * allocation, no synchronisation, capturable into a hipGraph.  Works on every handle, without an
+ * enable call, from the point where lbsim_step does: after a lbsim_reset of every env, a
+ * lbsim_set_state or a lbsim_state_load of every env.  LBSIM_EINVAL: a NULL or misaligned
+ * truth_out, or a handle before that point. */
+#define LBSIM_TRUTH_COLS 8
+int lbsim_ground_truth(lbsim_t* h, float* truth_out, void* stream);
+size_t lbsim_ground_truth_cols(void);
+
 /* ---- action latency (per-env control delay applied inside the step) ----
  * On an enabled handle the weights derived from an action come into force delay_us[b] after the
  * start of the step they were passed to, 0 <= delay_us <= M * dt (dt = step_interval in us, M =

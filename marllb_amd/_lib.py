@@ -209,6 +209,8 @@ _SIGNATURES = {
                                               ctypes.c_int32, ctypes.c_int32, _P]),
     "lbsim_clear_server_avail": (ctypes.c_int, [_P]),
     "lbsim_get_server_avail": (ctypes.c_int, [_P, _P, _P, _P, _P]),
+    "lbsim_ground_truth": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_ground_truth_cols": (ctypes.c_size_t, []),
     "lbsim_alias_tables": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P]),
     "lbsim_vose_tables": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P]),
     "lbsim_vose_sample": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, _P, ctypes.c_int64,

@@ -26,6 +26,7 @@
 #include "lbsim_nets.h"
 #include "lbsim_snapshot.h"
 #include "lbsim_stateless.h"
+#include "lbsim_truth.h"
 #include "lbsim_vpp.h"
 
 using namespace lbk;
@@ -496,6 +497,73 @@ __global__ void __launch_bounds__(256)
     if (env_out != nullptr) env_out[b] = per_env[row];
     if (phase_out != nullptr) phase_out[b] = (int32_t)phase;
   }
+}
+
+// ---- ground-truth server state (lbsim_ground_truth; the rule: lbsim_truth.h)
+static_assert(kTruthCols == LBSIM_TRUTH_COLS && kTruthCols == 8, "a row is two 16-byte stores");
+static_assert(kHcHead == 0x7FFFu, "truth_head restates the mask for its host build");
+
+// What the kernel reads, all by value: the state's arrays (hc, ring and ep_step of DevState) and
+// the optional ones, nullptr where the handle has none -- down, hidden (the lost_on section of a
+// cross-traffic handle only: elsewhere its words count lost-FIN flows), workers, and server, the
+// rates in flows/s: a schedule's live table [B * P, S] (P >= 1), the per-env live array [B, S]
+// (P = 0), or nullptr: the config's mu[].  Arguments of this kernel alone, not a part of DevState
+// or SimParams (§3.11).
+struct TruthArgs {
+  const uint32_t* hc;
+  const int2* ring;
+  const int32_t* ep_step;
+  const uint32_t* down;
+  const uint32_t* hidden;
+  const int32_t* workers;
+  const float* server;
+  int32_t B, S, Q;
+  int32_t P, H, wrap, max_steps, next_reset;
+  float mu[MAX_S];
+};
+
+// The ring of one server, by queue position.  The index is clamped into the ring: a state whose hc
+// word breaks n <= Q, head < Q (only lbsim_set_state could load one) reads no other memory.
+struct TruthRing {
+  const int2* ring;
+  int head, Q;
+  __device__ __forceinline__ int2 get(int pos) const {
+    const uint32_t r = (uint32_t)workers_ring_index(head, pos, Q);
+    return ring[r < (uint32_t)Q ? r : (uint32_t)Q - 1u];
+  }
+};
+
+// One lane per (env, server): coalesced loads of the server's words, at most two scattered 8-byte
+// ring loads (none from an empty queue, one where n - c == n - 1), the row as two 16-byte stores.
+// The rate is that of the env's next step launch: rate_gather_kernel's phase.
+__global__ void __launch_bounds__(256) ground_truth_kernel(TruthArgs a, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)a.B * a.S) return;
+  const int64_t b = i / a.S;
+  const int s = (int)(i - b * a.S);
+  const uint32_t hc = a.hc[i];
+  const int32_t c = a.workers != nullptr ? a.workers[i] : 1;
+  const int32_t lost = a.hidden != nullptr ? (int32_t)a.hidden[i] : 0;
+  const bool down = a.down != nullptr && a.down[i] != 0u;
+  float mu;
+  if (a.server != nullptr) {
+    int64_t row = b;
+    if (a.P > 1) {
+      const int32_t k = a.ep_step[b];
+      const uint32_t phase = (a.next_reset && k >= a.max_steps)
+                                 ? 0u : sched_phase(k, (uint32_t)a.P, (uint32_t)a.H, a.wrap != 0);
+      row = b * a.P + (int64_t)phase;
+    }
+    mu = a.server[row * a.S + s];
+  } else {
+    mu = a.mu[s];
+  }
+  const TruthRing q{a.ring + (size_t)i * (size_t)a.Q, truth_head(hc), a.Q};
+  float r[kTruthCols];
+  truth_row(q, hc, c, lost, down, mu, r);
+  float4* const o = reinterpret_cast<float4*>(out) + 2 * i;
+  o[0] = make_float4(r[0], r[1], r[2], r[3]);
+  o[1] = make_float4(r[4], r[5], r[6], r[7]);
 }
 
 // A trace schedule's ids (lbsim_set_trace_schedule) expanded to B rows: out[b * P + phase] =
@@ -2168,6 +2236,37 @@ int lbsim_get_server_workers(lbsim_t* h, int32_t* workers_out, void* stream) {
                      (hipStream_t)stream) != hipSuccess)
     return fail(h, LBSIM_EDEVICE, "server workers: device copy failed");
   return LBSIM_OK;
+}
+
+size_t lbsim_ground_truth_cols(void) { return (size_t)LBSIM_TRUTH_COLS; }
+
+int lbsim_ground_truth(lbsim_t* h, float* truth_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (truth_out == nullptr) return fail(h, LBSIM_EINVAL, "ground truth: truth_out is NULL");
+  if (((uintptr_t)truth_out & 15u) != 0u)
+    return fail(h, LBSIM_EINVAL, "ground truth: truth_out must be aligned to 16 bytes");
+  if (!h->initialised)
+    return fail(h, LBSIM_EINVAL, "call lbsim_reset before lbsim_ground_truth");
+  DeviceGuard g(h->device);
+  TruthArgs a{};
+  a.hc = h->st.hc;
+  a.ring = h->st.ring;
+  a.ep_step = h->st.ep_step;
+  a.down = h->st.down;
+  a.hidden = h->cross_buf != nullptr ? h->st.lost_on : nullptr;
+  a.workers = h->workers.c;
+  a.B = h->B, a.S = h->S, a.Q = h->Q;
+  a.max_steps = h->prm.max_steps, a.next_reset = h->prm.next_reset;
+  if (h->sched_P > 0) {  // the phase's row of the schedule's table
+    a.server = sched_live(h, h->sched_buf, h->sched_P).server;
+    a.P = h->sched_P, a.H = h->sched_H, a.wrap = h->sched_wrap;
+  } else if (h->rates_buf != nullptr) {  // the per-env array (the config's rates while none are set)
+    a.server = env_rates_live(h).server;
+  }
+  for (int k = 0; k < MAX_S; ++k) a.mu[k] = k < h->S ? h->cfg.server_rate[k] : 1.0f;
+  hipLaunchKernelGGL(ground_truth_kernel, dim3(blocks256((size_t)h->B * h->S)), dim3(256), 0,
+                     (hipStream_t)stream, a, truth_out);
+  return launch_check(h, "ground_truth_kernel");
 }
 
 int lbsim_clear_server_workers(lbsim_t* h, void* stream) {

@@ -40,6 +40,10 @@ FEATURE_NAMES = [
 ]
 DEFAULT_DISCRETE_WEIGHTS = [1.0, 1.5, 2.0]  # env.py:69
 
+# columns of a ground-truth row (lbsim_ground_truth)
+GROUND_TRUTH_COLUMNS = ("n_total", "n_hidden", "busy", "cpu", "wait_s", "backlog_s", "up",
+                        "capacity")
+
 
 def action_to_weights(action, action_type: str, discrete_weights, min_weight: float,
                       max_weight: float) -> np.ndarray:
@@ -70,7 +74,8 @@ def dict_to_array(obs_dict: dict, num_servers: int) -> np.ndarray:
 
 def make_spaces(num_servers: int, action_type: str, discrete_weights, min_weight: float,
                 max_weight: float, use_ground_truth: bool = False):
-    """env.py:156-184 (observation space is (S, 11 [+3]) even though arrays are (S, 11))."""
+    """env.py:156-184 (observation space is (S, 11 [+3]); the reference's arrays stay (S, 11),
+    LoadBalanceEnv(ground_truth_source="sim") fills the three columns)."""
     num_features = 11 + (3 if use_ground_truth else 0)
     obs_space = Box(low=0, high=np.inf, shape=(num_servers, num_features), dtype=np.float32)
     if action_type == "discrete":
@@ -596,6 +601,13 @@ class Handle:
             ctypes.c_void_p(phase.data_ptr()), ctypes.c_void_p(self._stream())))
         return want, now, phase
 
+    def ground_truth(self, out) -> None:
+        """The true server state into out, a contiguous (B, S, 8) float32 tensor on the handle's
+        device (lbsim_ground_truth): one kernel on the current stream, valid after any reset or
+        step, on every kind of handle."""
+        self.check(self.lib.lbsim_ground_truth(self.h, ctypes.c_void_p(out.data_ptr()),
+                                               ctypes.c_void_p(self._stream())))
+
     def lost_fin_overflow(self) -> np.ndarray:
         """Per env (B,) uint32: the lost-FIN guesses dropped at a full pending ring this episode
         (the snapshot's last section, lf_over); zeros on a handle without lost-FIN."""
@@ -630,6 +642,7 @@ class VecLoadBalanceEnv:
 
     reset(mask=None) -> obs (B, S, 11) f32 cuda tensor
     step(actions)    -> obs, reward (B,) f32, done (B,) bool, info dict of tensors
+    ground_truth()   -> (B, S, 8) f32: the servers' true state, for a critic
     Actions: (B, S) int32/int64 indices (discrete) or float32 weights (continuous), any device.
     Discrete indices follow Python list indexing for -n <= a < n (env.py:346); out-of-range
     indices are CLAMPED on the device (a >= n -> n-1, a < -n -> 0) where the reference raises
@@ -965,6 +978,35 @@ class VecLoadBalanceEnv:
     def clear_rates(self) -> None:
         """Back to the config's shared arrival_rate / server_rates."""
         self.handle.clear_env_rates()
+
+    # ---- ground-truth server state (DESIGN.md §3.20)
+    def ground_truth(self, out=None):
+        """(B, S, 8) f32 device tensor, columns GROUND_TRUTH_COLUMNS: what the simulator knows
+        about each server now and the observation does not show -- n_total (every flow in the
+        system, hidden cross traffic and flows in service included), n_hidden, busy (workers in
+        use), cpu (busy / workers), wait_s (seconds until a worker is free for a flow arriving
+        now), backlog_s (seconds until the server drains with no further arrival), up (0 while the
+        server is down) and capacity (workers * server_rate at the rates of the env's next step,
+        flows/s).  For a centralised critic or mixer during training; never normalised.  It
+        describes the state as it stands after the last reset() or step(): after a same-step
+        auto-reset that is the new episode's first state, not the one terminal_obs saw.  One small
+        kernel on the current stream, no allocation inside the library and no synchronisation, so
+        a step() followed by ground_truth() can be captured into a graph.  out: a contiguous
+        (B, S, 8) float32 tensor on the env's device to write into; by default a new tensor, or
+        (graph_mode) the same buffer every call.  Works on every env, whatever options it was
+        made with."""
+        torch = _torch()
+        shape = (self.num_envs, self.num_servers, len(GROUND_TRUTH_COLUMNS))
+        if out is None:
+            out = self._buf("truth", shape, torch.float32)
+        elif (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"out: expected a contiguous float32 tensor of shape {shape} on "
+                             f"{self.device}")
+        if not self._reset_done:
+            raise RuntimeError("ground_truth() before reset()")
+        self.handle.ground_truth(out)
+        return out
 
     # ---- hidden cross traffic (cross_traffic=True; DESIGN.md §3.17)
     def set_cross_traffic(self, share, weights=None) -> None:
@@ -1516,6 +1558,12 @@ class LoadBalanceEnv:
       reference_plumbing=True BASELINE configs[0]: the reference's own CPU simulation mode
                               (MT19937 random observations, marllb_amd/plumbing.py), host only,
                               byte-identical to env.py for the same seed; opt-in, never a fallback
+    use_ground_truth=True announces an (S, 14) observation space, as the reference does.  With
+    ground_truth_source="reference" (the default) the arrays stay (S, 11), as the reference's do;
+    with "sim" reset() / step() / restore() return (S, 14) float32 arrays whose columns 11-13
+    are the simulator's true cpu (busy workers / workers), memory (flows in the system /
+    queue_capacity) and busy workers, never normalised; ValueError with use_shm
+    or reference_plumbing.  ground_truth() returns the full (S, 8) rows.
     """
 
     DEFAULT_DISCRETE_WEIGHTS = DEFAULT_DISCRETE_WEIGHTS
@@ -1527,7 +1575,17 @@ class LoadBalanceEnv:
                  max_steps: int = 10000, use_shm: bool = False, shm_name: Optional[str] = None,
                  use_ground_truth: bool = False, normalize_obs: bool = False,
                  seed: Optional[int] = None, *, device=None, reference_plumbing: bool = False,
-                 **sim_kwargs):
+                 ground_truth_source: str = "reference", **sim_kwargs):
+        if ground_truth_source not in ("reference", "sim"):
+            raise ValueError(f"Unknown ground_truth_source: {ground_truth_source}")
+        # "sim" with use_ground_truth: reset() / step() return (S, 14) arrays whose columns 11-13
+        # are the simulator's cpu, n_total / queue_capacity and busy
+        self._truth_cols = bool(use_ground_truth) and ground_truth_source == "sim"
+        if self._truth_cols and (use_shm or reference_plumbing):
+            raise ValueError("ground_truth_source='sim' needs the GPU simulator (not use_shm or "
+                             "reference_plumbing): frames and the reference's plumbing carry no "
+                             "server state")
+        self.ground_truth_source = ground_truth_source
         self.num_servers = num_servers
         self.action_type = action_type
         self.discrete_weights = discrete_weights or self.DEFAULT_DISCRETE_WEIGHTS
@@ -1628,7 +1686,25 @@ class LoadBalanceEnv:
         self._cur_obs = (self._seq, obs)  # snapshot(): the observation in force until a step
         if self._host_norm:
             obs = self._normalize_host(obs)
-        return obs
+        return self._with_truth(obs)
+
+    def _with_truth(self, obs: np.ndarray) -> np.ndarray:
+        """ground_truth_source="sim": the (S, 11) observation widened to the announced (S, 14) by
+        the true cpu (busy / workers), memory (n_total / queue_capacity, the share of connection
+        slots held) and busy workers of the state as it stands; never normalised."""
+        if not self._truth_cols:
+            return obs
+        t = self.ground_truth()
+        q = np.float32(self._vec.cfg.queue_capacity)
+        return np.concatenate([obs, t[:, 3:4], t[:, 0:1] / q, t[:, 2:3]], axis=1)
+
+    def ground_truth(self) -> np.ndarray:
+        """(S, 8) float32, columns marllb_amd.GROUND_TRUTH_COLUMNS: the servers' true state after
+        the last reset() / step() (VecLoadBalanceEnv.ground_truth of the one env)."""
+        if self._vec is None or self.shm is not None:
+            raise RuntimeError("ground_truth needs the GPU simulator (not use_shm or "
+                               "reference_plumbing)")
+        return self._vec.ground_truth()[0].cpu().numpy()
 
     def _sim_step(self, idx_or_w: np.ndarray):
         """One simulator step -> (obs, raw obs, reward), zero-copy through pinned host memory."""
@@ -1819,6 +1895,7 @@ class LoadBalanceEnv:
             weights = wa.tolist()
             act = np.asarray(action).reshape(-1).astype(np.float32)
         next_obs, raw, reward = self._sim_step(act)
+        next_obs = self._with_truth(next_obs)
         self._last_raw = raw
         self._last_obs_dict = None  # built when render asks (env.py:391-423)
         self._last_obs_step = self.current_step
@@ -2000,7 +2077,7 @@ class LoadBalanceEnv:
         self.episode_rewards = list(snap.host["episode_rewards"])
         self._last_raw = snap.host["last_raw"]
         self._cur_obs = (self._seq, obs)
-        return obs.copy()
+        return self._with_truth(obs.copy())
 
     def render(self, mode: str = "human"):
         if mode == "human":

@@ -133,6 +133,7 @@ class VecMultiAgentLoadBalanceEnv:
     reset(mask=None)  -> obs (B, A, 4k + 7S) f32
     step(actions)     -> obs (B, A, D), rewards (B, A), done (B,), info
     get_state()       -> (B, 4S + 10) f32 (the wrapper's simulation-mode state)
+    true_state()      -> (B, 8S) f32 (the servers' ground truth)
     actions: (B, A) one value per agent (broadcast to its k servers), (B, A, k) or (B, S).
     """
 
@@ -234,6 +235,14 @@ class VecMultiAgentLoadBalanceEnv:
         if self._state is None:
             raise RuntimeError("call reset() before get_state()")
         return self._state
+
+    def true_state(self, out=None):
+        """(B, 8 S) f32: the servers' ground-truth rows (VecLoadBalanceEnv.ground_truth, columns
+        marllb_amd.GROUND_TRUTH_COLUMNS) flattened server-major in agent order, for a mixer or a
+        centralised critic during training: what get_state()'s zeros(4 S) stand in for.  The state
+        as it stands after the last reset() / step(); get_state() is unchanged.  out: a contiguous
+        (B, S, 8) float32 tensor to write into."""
+        return self.vec.ground_truth(out).view(self.num_envs, 8 * self.S)
 
     def set_rates(self, arrival_rate=None, server_rates=None) -> None:
         """Per-env arrival (B,) / server (B, S) rates: VecLoadBalanceEnv.set_rates."""
