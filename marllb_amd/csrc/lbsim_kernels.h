@@ -2657,10 +2657,19 @@ __device__ __forceinline__ void observe_rows_paired_regs(const DevState& st, con
 // INC: unchanged rows take their cached features unless some env was reset by this step (nr:
 // next-step auto-reset is on; its ep_step words are loaded with the decision words); rows
 // the register path cannot take (n < 8, a sample >= kPackLimit) go through observe_chunk per env.
-template <bool INC>
+// arrived(): called once the decision words are in (observe_pair_kernel parks the episode words
+// it requested with them).
+// (requesting the rows' cached features with the decision words as well, for one round trip on
+// the unchanged path, took observe_pair_kernel<0, false> from 6 to 10 spilled VGPRs and 28 to
+// 44 B of scratch per lane: not run, profiles/obs_trips/)
+struct NoHook {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <bool INC, typename Hook = NoHook>
 __device__ __forceinline__ void observe_rows_paired(const DevState& st, const SimParams& p,
                                                     size_t b0, int nenv, ObsScratch& sc,
-                                                    float* obs_out, int lane) {
+                                                    float* obs_out, int lane,
+                                                    Hook arrived = Hook()) {
   const int S = p.S, nrows = nenv * S;
   const size_t row0 = b0 * (size_t)S;
   const int u = lane >> 3;
@@ -2671,7 +2680,9 @@ __device__ __forceinline__ void observe_rows_paired(const DevState& st, const Si
   if constexpr (INC) {
     const uint32_t w = lane < 4 * nrows ? st.chg[(row0 + (size_t)(lane >> 2)) * 4 + (lane & 3)] : 0u;
     // one round trip for the decision words (a reset env's rows are marked written: no reset flag)
-    if (!__any(w != 0u)) {  // no reservoir of the rows changed: the cached features
+    const bool same = !__any(w != 0u);
+    arrived();
+    if (same) {  // no reservoir of the rows changed: the cached features
       for (int e = lane; e < nrows * NF; e += 64) {
         const int s = e / NF, c = e - s * NF;
         obs_out[e] = c == 0 ? n_flow_on(st, row0 + (size_t)s)
@@ -2680,6 +2691,8 @@ __device__ __forceinline__ void observe_rows_paired(const DevState& st, const Si
       wave_sync();
       return;
     }
+  } else {
+    arrived();
   }
   const int n = rc < (uint32_t)K ? (int)rc : K;
   if (!__any(act && (n < 8 || (hcw & kHcBig) != 0u))) {
@@ -2887,9 +2900,130 @@ __global__ void __launch_bounds__(64 * kObsWavesPerEnv<MAXS>, 5)
   observe_outputs<MAXS, MODE, FAC>(st, p, out, b, s_obs, s_act, tid, nthr);
 }
 
+// observe_outputs for the nenv = 8 / S envs [b0, b0 + nenv) of one observe_pair_kernel wave at
+// once, their nenv * S <= 8 rows back to back in s_obs: lane r scans row r (one ballot for the
+// wave), lane e computes env b0 + e's reward and episode words -- the same operations in the same
+// order per env as observe_outputs' lane 0, so the same bits -- and the rows, being consecutive
+// in every output, copy out in one pass.  es0 / er0: lane e's ep_step / ep_return words of env
+// b0 + e, loaded by the kernel with the decision words (no env belongs to two waves of a launch);
+// nothing here loads them again.  Normalisation and the facade rows stay per env behind their
+// wave-uniform tests.
+template <int MODE, bool FAC>
+__device__ __forceinline__ void observe_pair_outputs(const DevState& st, const SimParams& p,
+                                                     const ObsOutputs& out, size_t b0, int nenv,
+                                                     float* s_obs, float* s_act, int lane,
+                                                     int32_t es0, double er0) {
+  const int S = p.S, nrows = nenv * S, nobs = S * NF;
+  // active servers (any column > 0) of all the rows; each env's reward-field values compacted
+  // into s_act + e * S in server order
+  bool act = false;
+  if (lane < nrows)
+    for (int f = 0; f < NF; ++f) act |= s_obs[lane * NF + f] > 0.0f;
+  const uint32_t act_mask = (uint32_t)__ballot(act);
+  const bool fok = p.reward_field >= 0 && p.reward_field < NF;
+  if (act && fok) {  // lane < nrows <= 8
+    int e = 0;       // lane / S
+    for (int k = 1; k < 8; ++k) e += lane >= k * S ? 1 : 0;
+    const int s = lane - e * S;
+    s_act[e * S + __popc((act_mask >> (e * S)) & ((1u << s) - 1u))] =
+        s_obs[lane * NF + p.reward_field];
+  }
+  wave_sync();
+  int32_t es = es0;  // the episode step after this launch (reset mode: as the dynamics left it)
+  if (MODE == kModeStep && lane < nenv) {
+    const size_t b = b0 + (size_t)lane;
+    const int na = __popc((act_mask >> (lane * S)) & ((1u << S) - 1u));
+    const float* sa = s_act + lane * S;
+    double r = 0.0;
+    // reset by this step (next-step auto-reset, ep_step = -1): reward 0, episode step 0, not done
+    const bool fresh = p.next_reset && es0 < 0;
+    if (fok && !fresh) {
+      if (S <= kObsChunk && p.reward_metric == 0)
+        r = jain_upto4(na, sa);
+      else
+        r = reward_values(na, [&](int i) { return (double)sa[i]; }, p.reward_metric);
+    }
+    out.reward[b] = (float)r;
+    es = es0 + 1;  // -1 + 1 = 0 for a fresh env
+    const double er = er0 + r;  // 0 + 0
+    st.ep_step[b] = es;
+    st.ep_return[b] = er;
+    out.done[b] = (uint8_t)(es >= p.max_steps ? 1 : 0);
+    if (out.ep_len != nullptr) out.ep_len[b] = es;
+    if (out.ep_ret != nullptr) out.ep_ret[b] = er;
+  }
+
+  const int ntot = nrows * NF;
+  const size_t g0 = b0 * (size_t)nobs;
+  const bool facade = FAC && (out.agent_obs != nullptr || out.state != nullptr);
+  if (out.raw_obs != nullptr)
+    for (int e = lane; e < ntot; e += 64) out.raw_obs[g0 + (size_t)e] = s_obs[e];
+  if (p.normalize) {  // env.py:460-468, float64 running statistics
+    for (int v = 0; v < nenv; ++v) {
+      const size_t b = b0 + (size_t)v;
+      float* so = s_obs + v * nobs;
+      const int32_t cnt = st.norm_count[b] + 1;
+      for (int e = lane; e < nobs; e += 64) {
+        const size_t gi = b * (size_t)nobs + (size_t)e;
+        const double o = (double)so[e];
+        double m = st.norm_mean[gi];
+        const double sdv = st.norm_std[gi];
+        const double delta = o - m;
+        m = m + delta / (double)cnt;
+        const double delta2 = o - m;
+        double var = (sdv * sdv * (double)(cnt - 1) + delta * delta2) / (double)cnt;
+        var = var > 1e-8 ? var : 1e-8;
+        const double ns = sqrt(var);
+        st.norm_mean[gi] = m;
+        st.norm_std[gi] = ns;
+        const float r = (float)((o - m) / (ns + 1e-8));
+        out.obs[gi] = r;
+        if (facade) so[e] = r;  // the returned rows, for the facade gather below (same thread)
+      }
+      if (lane == 0) st.norm_count[b] = cnt;
+    }
+  } else {
+    for (int e = lane; e < ntot; e += 64) out.obs[g0 + (size_t)e] = s_obs[e];
+  }
+  if constexpr (FAC) {
+    if (facade) {
+      wave_sync();
+      const int A = out.num_agents, k = out.servers_per_agent, D = 4 * k + 7 * S;
+      for (int v = 0; v < nenv; ++v) {
+        const size_t b = b0 + (size_t)v;
+        const float* so = s_obs + v * nobs;
+        const int32_t es_v = __shfl(es, v, 64);  // env v's episode step, from its lane
+        if (out.agent_obs != nullptr) {  // agent a: flat[4 a k, 4 (a+1) k) ++ flat[4 S:]
+          float* ao = out.agent_obs + b * (size_t)A * (size_t)D;
+          for (int e = lane; e < A * D; e += 64) {
+            const int a = e / D, j = e - a * D;
+            ao[e] = so[j < 4 * k ? 4 * k * a + j : 4 * S + (j - 4 * k)];
+          }
+        }
+        if (out.state != nullptr) {  // get_state: zeros ... then step / max_steps, num_agents
+          const int sd = 4 * S + 10;
+          float* go = out.state + b * (size_t)sd;
+          for (int e = lane; e < sd - 2; e += 64) go[e] = 0.0f;
+          if (lane == 0) {
+            go[sd - 2] = (float)es_v / (float)p.max_steps;
+            go[sd - 1] = (float)A;
+          }
+        }
+      }
+    }
+  }
+  if (out.done_word != nullptr) {  // one-env handles: the completion word, after every output
+    wave_sync();
+    __threadfence_system();
+    if (lane == 0)
+      __hip_atomic_store(out.done_word, out.done_value, __ATOMIC_RELEASE,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 // Step-mode observation when every record pairs dur == fct (observe_rows_paired): one wave per
-// 8 / S whole envs (S <= 8: their 8 / S * S <= 8 consecutive rows), then each env's reward,
-// episode words and outputs (observe_outputs, in env order).
+// 8 / S whole envs (S <= 8: their 8 / S * S <= 8 consecutive rows), then the envs' rewards,
+// episode words and outputs (observe_pair_outputs: lane e does env e).
 // 4 waves per SIMD (128 VGPRs): with 5 (96 VGPRs) the register path spilled and the kernel ran
 // 140 us against 130 us at 65536 x 4, 255 against 236 us at 65536 x 8 (profiles/r05d/).
 constexpr int kObsPairWaves = 4;
@@ -2902,13 +3036,30 @@ __global__ void __launch_bounds__(64, kObsPairWaves)
   const int S = p.S, epw = 8 / S, lane = (int)threadIdx.x;
   const size_t b0 = (size_t)blockIdx.x * (size_t)epw;
   const int nenv = (size_t)p.B - b0 < (size_t)epw ? (int)((size_t)p.B - b0) : epw;
-  // (loading the envs' episode words into LDS up front with global_load_lds measured 12 us slower
-  // at 65536 x 4: 92.8 -> 104.5 us, profiles/r06e/)
-  observe_rows_paired<MODE == kModeStep>(st, p, b0, nenv, sc, s_obs, lane);
-  for (int e = 0; e < nenv; ++e) {
-    observe_outputs<8, MODE, FAC>(st, p, out, b0 + (size_t)e, s_obs + e * S * NF, s_act, lane, 64);
-    wave_sync();  // s_act reused by the next env
-  }
+  // The episode words of env b0 + lane (lanes past nenv: env b0's), requested here by plain
+  // vector loads so that they travel with observe_rows_paired's decision words (one round trip);
+  // once those are in they are parked in LDS by a plain ds_write (held in registers through the
+  // register path they cost 2 more spilled VGPRs) and read back by observe_pair_outputs: loaded
+  // there, env by env, they were two more serial round trips per wave at S = 4
+  // (profiles/obs_trips/).  Next-step auto-reset: the dynamics launch before this one wrote
+  // ep_step = -1 for the envs it reset.
+  // (loading them into LDS with global_load_lds measured 12 us slower at 65536 x 4:
+  // 92.8 -> 104.5 us, profiles/r06e/)
+  __shared__ int32_t s_es[8];
+  __shared__ double s_er[8];
+  const size_t be = b0 + (size_t)(lane < nenv ? lane : 0);
+  const int32_t es_l = st.ep_step[be];
+  const double er_l = MODE == kModeStep ? st.ep_return[be] : 0.0;
+  const auto park = [&]() {
+    if (lane < 8) {
+      s_es[lane] = es_l;
+      s_er[lane] = er_l;
+    }
+  };
+  observe_rows_paired<MODE == kModeStep>(st, p, b0, nenv, sc, s_obs, lane, park);
+  // (lane e reads back the words it parked itself)
+  observe_pair_outputs<MODE, FAC>(st, p, out, b0, nenv, s_obs, s_act, lane, s_es[lane & 7],
+                                  s_er[lane & 7]);
 }
 
 // Step-mode observation of paired records for S = 16 (configs[4]'s 4 agents x 4 servers): one
