@@ -123,7 +123,8 @@ enum lbsim_dyn_mapping {
 enum lbsim_dyn_kernel {
   LBSIM_DYN_KERNEL_ENV_LANE = 0,  /* dynamics_kernel: one lane per env                        */
   LBSIM_DYN_KERNEL_GROUP = 1,     /* dynamics_group_kernel: one lane per server, G-lane groups */
-  LBSIM_DYN_KERNEL_WAVE = 2       /* dynamics_wave_kernel: one wave per env                    */
+  LBSIM_DYN_KERNEL_WAVE = 2,      /* dynamics_wave_kernel: one wave per env                    */
+  LBSIM_DYN_KERNEL_POOL = 3       /* dynamics_pool_kernel: one G-lane group per server pool    */
 };
 
 /* How lbsim_step runs; every choice produces the same bits.  FUSED: one launch per step whose
@@ -812,6 +813,49 @@ int lbsim_action_delay_save(lbsim_t* h, void* dev_buf, size_t bytes, const uint8
                             void* stream);
 int lbsim_action_delay_load(lbsim_t* h, const void* dev_buf, size_t bytes, const int32_t* src_env,
                             void* stream);
+
+/* Shared server pools: several balancers in front of ONE set of servers.
+ * A = `balancers` consecutive envs of the handle form a pool: pool c is envs cA .. cA + A - 1,
+ * and its members share one physical set of S FIFO servers.  Every env stays one balancer with
+ * its own arrival stream (exactly the one it would have alone), action row, (S, 11) observation,
+ * reward, reservoirs, drops and assign counts; only the queues are shared.  One event loop per
+ * pool: the earliest completion due no later than the pool's next arrival goes first, else the
+ * next arrival, the smallest next_arr over the members (ties: the lowest member).  Member a's
+ * arrival is assigned by its own weight row and its OWN flows in flight n_own[a][s] (SED / SED2
+ * scores, LSQ / LSQ2 counts; the hashes from its own words), a server is eligible while its
+ * PHYSICAL queue is below queue_capacity, and a flow with no eligible server counts in member
+ * a's `dropped`.  A flow starts at max(ta, tc of the last queued flow, whoever owns it); its
+ * sample tc - ta goes into its owner's reservoir (gid_owner, s) under the unchanged rule.
+ * Observation column 0 of member a is n_own[a][s]: bits 16-31 of its hc[b, s] hold its own count
+ * and bit 15 its own big flag.  lbsim_reset resets a pool iff any member's mask byte is set, and
+ * then every member of it (so ep_step, clock and done are equal across a pool).  With balancers
+ * = 1 results equal a handle that was not enabled, bit for bit.
+ * lbsim_server_pool_enable: before the handle's first lbsim_reset (LBSIM_EINVAL after it; a
+ * second call with the same value is a no-op).  LBSIM_EINVAL for balancers outside [1, 8],
+ * num_envs % balancers != 0 or env_id_offset % balancers != 0 (a pool never straddles a shard).
+ * LBSIM_ENOTSUP, the message naming the option, with num_servers > 16, assign_policy ALIAS,
+ * arrival_source TRACE, lost_fin_prob > 0, fail_prob > 0, reservoir_mode VPP, n_flow_on_mode
+ * VPP, duration_mode SERVICE or next_step_reset, and on a handle with flow statistics, workload
+ * tables, server availability, cross traffic, server workers, action delay, a rate or trace
+ * schedule, or per-env rates in force (they may hold per-env server rates: call
+ * lbsim_clear_env_rates, enable, then set the arrival rates again).  On an enabled handle those
+ * opt-ins, a non-NULL server_rate in lbsim_set_env_rates, and lbsim_state_save /
+ * lbsim_state_load (a per-env fork would tear a pool apart) return LBSIM_ENOTSUP.  Per-env
+ * arrival rates (unequal ECMP splits),
+ * normalize_obs, both action types, lbsim_step_ex's outputs, lbsim_episode_stats,
+ * lbsim_vpp_export, lbsim_get_state / lbsim_set_state and hipGraph capture of lbsim_step work as
+ * on any handle.  The steps launch dynamics_pool_kernel (lbsim_dynamics_kernel:
+ * LBSIM_DYN_KERNEL_POOL) and the handle's ordinary observe; no allocation or synchronisation is
+ * added to lbsim_step or lbsim_reset.
+ * The state gains two sections after all the others (lbsim_state_size counts them): pool_hc
+ * [C, S] u32, the physical FIFO's ring head | count << 16, and pool_owner [C, S, Q] u8, the
+ * member that owns each ring entry; the entries {tc, ta} are the first member's ring rows.
+ * lbsim_ground_truth on an enabled handle describes the physical server in every member's row:
+ * n_total the physical queue length, n_hidden that minus the member's own count (what the other
+ * balancers put there), busy / cpu / wait_s / backlog_s of the physical FIFO, up 1, capacity mu.
+ * lbsim_server_pool_size: A, or 0 on a handle that was not enabled. */
+int lbsim_server_pool_enable(lbsim_t* h, int32_t balancers);
+int lbsim_server_pool_size(const lbsim_t* h);
 
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/

@@ -7,9 +7,11 @@ liblbsim.so), with the reference's Gym-style API on top.
 from .env import (FEATURE_NAMES, GROUND_TRUTH_COLUMNS, DeviceSnapshot, LoadBalanceEnv, LoadBalanceEnvGym,
                   VecLoadBalanceEnv, make_config)
 from .multi_agent import MultiAgentLoadBalanceEnv, VecMultiAgentLoadBalanceEnv
+from .pools import VecServerPoolEnv
 from .randomize import (burst_schedule, diurnal_schedule, outage_schedule,
                         rolling_restart_schedule, sample_action_delay, sample_cluster_sizes,
-                        sample_cross_traffic, sample_rates, sample_server_workers, schedule_phase)
+                        sample_cross_traffic, sample_pool_arrival_rates, sample_rates,
+                        sample_server_workers, schedule_phase)
 from .spaces import Box, MultiDiscrete
 from .workload import (TABLE_BINS, bounded_pareto_table, constant_table, empirical_table,
                        exponential_table, hyperexp_table, lognormal_table, quantile_table,
@@ -23,5 +25,6 @@ __all__ = ["FEATURE_NAMES", "LoadBalanceEnv", "LoadBalanceEnvGym", "VecLoadBalan
            "weibull_table", "constant_table", "empirical_table", "table_mean", "table_cv2",
            "sample_table_ids", "sample_cluster_sizes", "outage_schedule",
            "rolling_restart_schedule", "sample_cross_traffic", "sample_server_workers",
-           "sample_action_delay", "GROUND_TRUTH_COLUMNS"]
+           "sample_action_delay", "GROUND_TRUTH_COLUMNS", "VecServerPoolEnv",
+           "sample_pool_arrival_rates"]
 __version__ = "0.1.0"

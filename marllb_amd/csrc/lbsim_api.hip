@@ -132,6 +132,9 @@ struct lbsim {
   void* delay_buf = nullptr;
   ActionDelay delay{};  // the live arrays (null pointers: actions act at once)
   int32_t delay_M = 0;  // max_delay_steps
+  // lbsim_server_pool_enable: the physical FIFOs' words and owners (two state sections after all
+  // the others, sections() below) and the widened reset mask, allocated once and never moved
+  PoolArrays pool{};  // (A = 0: the handle has no pools)
   bool initialised;  // a full reset has been issued
   bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
@@ -154,6 +157,10 @@ int fail(lbsim_t* h, int code, const char* fmt, ...) {
   else g_create_err = buf;
   return code;
 }
+
+// An opt-in refused on a handle with shared server pools (not composed).
+const char kPoolNoCompose[] = "%s on a handle with shared server pools "
+                              "(lbsim_server_pool_enable): not supported together";
 
 // Scoped hipSetDevice that restores the caller's current device (torch keeps its own).
 struct DeviceGuard {
@@ -341,6 +348,12 @@ std::vector<Section> sections(lbsim_t* h) {
     v.push_back({(void**)&s.pend_hc, BS * 4});
     v.push_back({(void**)&s.pend, BS * (size_t)h->prm.pend_P * 8});
     v.push_back({(void**)&s.lf_over, B * 4});
+  }
+  // shared server pools: the physical FIFO of every (pool, server), after every other section
+  if (h->pool.A > 0) {
+    const size_t CS = BS / (size_t)h->pool.A;
+    v.push_back({(void**)&h->pool.hc, CS * 4});
+    v.push_back({(void**)&h->pool.owner, CS * h->Q});
   }
   return v;
 }
@@ -1197,6 +1210,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.cross_traffic = h->cross_buf != nullptr;
   in.server_workers = h->workers_buf != nullptr;
   in.action_delay = h->delay_buf != nullptr;
+  in.pool = h->pool.A;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -1204,6 +1218,11 @@ StepPlan plan_of(const lbsim_t* h) {
 int launch_dynamics(lbsim_t* h, const void* action, int dtype, int32_t* assign,
                     const uint8_t* mask, int mode, hipStream_t stream) {
   ProfScope ps(h, stream, mode == kModeStep ? 0 : 2);
+  if (h->pool.A > 0) {  // shared server pools: their own kernel (mask: the widened one)
+    if (mode == kModeStep) launch_dynamics_pool_step(ctx(h), h->pool, action, dtype, assign, stream);
+    else launch_dynamics_pool_reset(ctx(h), h->pool, mask, stream);
+    return launch_check(h, "dynamics_pool_kernel");
+  }
   if (mode == kModeStep && h->plan.nr)  // next-step auto-reset: done envs reset instead
     launch_dynamics_step_nr(ctx(h), action, dtype, assign, mask, stream);
   else if (mode == kModeStep)
@@ -1430,10 +1449,17 @@ int lbsim_reset_ex(lbsim_t* h, const uint8_t* env_mask, const lbsim_step_outputs
   if (rc != LBSIM_OK) return rc;
   rc = trace_select(h, env_mask, kModeReset, s);  // a trace schedule: the same
   if (rc != LBSIM_OK) return rc;
-  rc = launch_dynamics(h, nullptr, 0, nullptr, env_mask, kModeReset, s);
+  // shared server pools: a pool resets iff any member's byte is set, and then all of it.  The
+  // mask is widened here, once, for both launches: the observe kernels read one byte per env
+  const uint8_t* mask = env_mask;
+  if (h->pool.A > 1 && env_mask != nullptr) {
+    launch_pool_mask(h->pool, env_mask, h->B, s);
+    mask = h->pool.mask;
+  }
+  rc = launch_dynamics(h, nullptr, 0, nullptr, mask, kModeReset, s);
   if (rc != LBSIM_OK) return rc;
   const ObsOutputs o = obs_outputs(out, true);
-  rc = launch_observe(h, o, env_mask, kModeReset, s);
+  rc = launch_observe(h, o, mask, kModeReset, s);
   if (rc != LBSIM_OK) return rc;
   if (env_mask == nullptr) h->initialised = true;
   return LBSIM_OK;
@@ -1638,6 +1664,7 @@ int lbsim_set_trace_bank(lbsim_t* h, const uint32_t* gap_us, const float* work,
 int lbsim_set_trace_schedule(lbsim_t* h, const int32_t* trace_id, int rows, int P,
                              int steps_per_phase, int wrap, void* stream) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "a trace schedule");
   if (!h->prm.trace)
     return fail(h, LBSIM_EINVAL, "a trace schedule needs arrival_source TRACE");
   if (h->bank_begin.empty())
@@ -1749,6 +1776,7 @@ int lbsim_env_trace(lbsim_t* h, int32_t* trace_id_out, int32_t* phase_out, void*
 int lbsim_set_workload_tables(lbsim_t* h, const float* tables, int n_tables, const int32_t* gap_id,
                               const int32_t* work_id, int rows, void* stream) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "workload tables");
   if (h->prm.trace)
     return fail(h, LBSIM_EINVAL, "workload tables on a TRACE handle: the trace supplies gap and "
                                  "work");
@@ -1805,6 +1833,8 @@ int lbsim_clear_workload_tables(lbsim_t* h) {
 int lbsim_set_env_rates(lbsim_t* h, const float* arrival_rate, const float* server_rate,
                         void* stream) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0 && server_rate != nullptr)
+    return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "per-env server rates");
   if (arrival_rate != nullptr && h->prm.lf_thr != 0u)
     return fail(h, LBSIM_ENOTSUP, "per-env arrival rates on a lost-FIN handle (lost_fin_prob > 0): "
                                   "the bucket-wait mean and the 32-bit guess bound depend on the "
@@ -1907,6 +1937,7 @@ int lbsim_set_rate_schedule(lbsim_t* h, const float* arrival_rate, const float* 
                             int32_t rows, int32_t phases, int32_t steps_per_phase, int32_t wrap,
                             void* stream) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "a rate schedule");
   if (phases < 1 || phases > 4096)
     return fail(h, LBSIM_EINVAL, "rate schedule: phases must be in [1, 4096] (got %d)", phases);
   if (steps_per_phase < 1)
@@ -2029,6 +2060,7 @@ int lbsim_rate_phase(lbsim_t* h, int32_t* phase_out, void* stream) {
 
 int lbsim_flow_stats_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "flow statistics");
   if (h->flow_buf != nullptr) return LBSIM_OK;
   if (h->reset_seen)
     return fail(h, LBSIM_EINVAL, "lbsim_flow_stats_enable must precede the handle's first "
@@ -2054,6 +2086,7 @@ int lbsim_flow_stats_enable(lbsim_t* h) {
 
 int lbsim_cross_traffic_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "cross traffic");
   if (h->cross_buf != nullptr) return LBSIM_OK;
   if (h->prm.lf_thr != 0u)
     return fail(h, LBSIM_ENOTSUP, "cross traffic on a lost-FIN handle (lost_fin_prob > 0): the "
@@ -2159,6 +2192,7 @@ int lbsim_clear_cross_traffic(lbsim_t* h, void* stream) {
 
 int lbsim_server_workers_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "server workers");
   if (h->workers_buf != nullptr) return LBSIM_OK;
   if (h->prm.lf_thr != 0u)
     return fail(h, LBSIM_ENOTSUP, "server workers on a lost-FIN handle (lost_fin_prob > 0): the "
@@ -2248,6 +2282,10 @@ int lbsim_ground_truth(lbsim_t* h, float* truth_out, void* stream) {
   if (!h->initialised)
     return fail(h, LBSIM_EINVAL, "call lbsim_reset before lbsim_ground_truth");
   DeviceGuard g(h->device);
+  if (h->pool.A > 0) {  // shared server pools: the physical servers' rows
+    launch_pool_truth(ctx(h), h->pool, h->cfg.server_rate, truth_out, (hipStream_t)stream);
+    return launch_check(h, "pool_truth_kernel");
+  }
   TruthArgs a{};
   a.hc = h->st.hc;
   a.ring = h->st.ring;
@@ -2282,6 +2320,78 @@ int lbsim_clear_server_workers(lbsim_t* h, void* stream) {
   return launch_check(h, "workers_convert_kernel");
 }
 
+// ---- shared server pools (the rule: lbsim_pool.h, the kernels: lbsim_dyn_pool.hip)
+
+int lbsim_server_pool_enable(lbsim_t* h, int32_t balancers) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  switch (pool_enable_check(h->B, h->cfg.env_id_offset, balancers)) {
+    case 1:
+      return fail(h, LBSIM_EINVAL, "server pools: balancers must be in [1, %d] (got %d)",
+                  kPoolMaxBalancers, (int)balancers);
+    case 2:
+      return fail(h, LBSIM_EINVAL, "server pools: num_envs = %d is no multiple of balancers = %d",
+                  h->B, (int)balancers);
+    case 3:
+      return fail(h, LBSIM_EINVAL, "server pools: env_id_offset = %lld is no multiple of balancers "
+                                   "= %d (a pool never straddles a shard)",
+                  (long long)h->cfg.env_id_offset, (int)balancers);
+    default: break;
+  }
+  if (h->pool.A > 0) {
+    if (balancers == h->pool.A) return LBSIM_OK;
+    return fail(h, LBSIM_EINVAL, "server pools are already on with balancers = %d", (int)h->pool.A);
+  }
+  // what the pool kernel has no code for (marllb_amd/pools.py check_pool_config states the
+  // config's and the constructor's part of this list, with the same words, before a handle
+  // exists: keep the two together; tests/test_server_pools.py walks both)
+  const char* no = nullptr;
+  const lbsim_config_t& c = h->cfg;
+  if (h->S > kPoolMaxServers) no = "num_servers > 16";
+  else if (c.assign_policy == LBSIM_POLICY_ALIAS) no = "assign_policy ALIAS";
+  else if (c.arrival_source == LBSIM_ARRIVAL_TRACE) no = "arrival_source TRACE";
+  else if (c.lost_fin_prob > 0.0f) no = "lost_fin_prob > 0";
+  else if (c.fail_prob > 0.0f) no = "fail_prob > 0";
+  else if (c.reservoir_mode == LBSIM_RESERVOIR_VPP) no = "reservoir_mode VPP";
+  else if (c.n_flow_on_mode == LBSIM_NFLOW_VPP) no = "n_flow_on_mode VPP";
+  else if (c.duration_mode == LBSIM_DURATION_SERVICE) no = "duration_mode SERVICE";
+  else if (c.next_step_reset != 0) no = "next_step_reset";
+  else if (h->flow_buf != nullptr) no = "flow statistics";
+  else if (h->wtab_T > 0) no = "workload tables";
+  else if (h->avail_on) no = "server availability";
+  else if (h->cross_buf != nullptr) no = "cross traffic";
+  else if (h->workers_buf != nullptr) no = "server workers";
+  else if (h->delay_buf != nullptr) no = "action delay";
+  else if (h->sched_P > 0) no = "a rate schedule";
+  else if (h->rates_on)  // (they may hold per-env server rates, which a pool cannot have)
+    no = "per-env rates in force (lbsim_clear_env_rates, enable, then set the arrival rates)";
+  if (no != nullptr) return fail(h, LBSIM_ENOTSUP, "server pools with %s: not supported", no);
+  if (h->reset_seen)
+    return fail(h, LBSIM_EINVAL, "lbsim_server_pool_enable must precede the handle's first "
+                                 "lbsim_reset (it changes which kernels the handle launches)");
+  DeviceGuard g(h->device);
+  const size_t CS = (size_t)h->B / (size_t)balancers * (size_t)h->S;
+  const size_t bytes[3] = {CS * 4, CS * (size_t)h->Q, (size_t)h->B};
+  void* ptr[3] = {nullptr, nullptr, nullptr};
+  bool ok = true;
+  for (int i = 0; i < 3 && ok; ++i)
+    ok = hipMalloc(&ptr[i], bytes[i]) == hipSuccess && hipMemset(ptr[i], 0, bytes[i]) == hipSuccess;
+  ok = ok && hipDeviceSynchronize() == hipSuccess;
+  if (!ok) {
+    for (void* q : ptr)
+      if (q != nullptr) (void)hipFree(q);
+    return fail(h, LBSIM_ENOMEM, "server pools: device allocation failed");
+  }
+  for (void* q : ptr) h->allocs.push_back(q);
+  h->pool.hc = (uint32_t*)ptr[0];
+  h->pool.owner = (uint8_t*)ptr[1];
+  h->pool.mask = (uint8_t*)ptr[2];
+  h->pool.A = balancers;
+  h->plan = plan_of(h);  // the pool dynamics and the two-launch observe (make_plan)
+  return LBSIM_OK;
+}
+
+int lbsim_server_pool_size(const lbsim_t* h) { return h == nullptr ? 0 : (int)h->pool.A; }
+
 // ---- action latency (the rule and the kernels: lbsim_delay.h)
 namespace {
 const char kDelayOff[] = "action delay is off: call lbsim_action_delay_enable first";
@@ -2313,6 +2423,7 @@ int delay_gather(lbsim_t* h, const char* who, void* dev_buf, size_t bytes, const
 
 int lbsim_action_delay_enable(lbsim_t* h, int32_t max_delay_steps) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "action delay");
   if (!delay_steps_ok(max_delay_steps))
     return fail(h, LBSIM_EINVAL, "action delay: max_delay_steps must be in [1, %d] (got %d)",
                 (int)kMaxDelaySteps, (int)max_delay_steps);
@@ -2414,6 +2525,7 @@ int lbsim_action_delay_load(lbsim_t* h, const void* dev_buf, size_t bytes, const
 
 int lbsim_server_avail_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "server availability");
   if (h->avail_on) return LBSIM_OK;
   if (h->prm.fail_thr != 0u)
     return fail(h, LBSIM_ENOTSUP, "scripted availability on a handle with random failures "
@@ -2928,6 +3040,10 @@ namespace {
 int state_gather(lbsim_t* h, const char* who, void* dev_buf, size_t bytes, const uint8_t* mask,
                  const int32_t* src_env, int dir, void* stream) {
   if (h == nullptr) return fail(nullptr, LBSIM_EINVAL, "%s: handle is NULL", who);
+  if (h->pool.A > 0)
+    return fail(h, LBSIM_ENOTSUP, "%s on a handle with shared server pools: a per-env copy would "
+                                  "tear a pool apart (lbsim_get_state / lbsim_set_state carry "
+                                  "whole handles)", who);
   if (dev_buf == nullptr) return fail(h, LBSIM_EINVAL, "%s: dev_buf is NULL", who);
   if ((uintptr_t)dev_buf % 16u != 0)
     return fail(h, LBSIM_EINVAL, "%s: dev_buf must be 16-byte aligned", who);

@@ -8,6 +8,9 @@
 //                      (host-only; the launchers below turn the plan into template arguments)
 //   lbsim_dyn_delay.hip  dynamics_group_delay_kernel launchers (action latency); built twice
 //                      (-DLBSIM_DYN_MODE=0 step, 2 step_nr)
+//   lbsim_pool.h       shared server pools: the host / device rule of a pool and its physical FIFOs
+//   lbsim_dyn_pool.hip  dynamics_pool_kernel launchers (shared server pools); built twice
+//                      (-DLBSIM_DYN_MODE=0 step, 1 reset, with the pool handle's two small kernels)
 //   lbsim_dyn.hip      dynamics_kernel / dynamics_group_kernel launchers; built three times
 //                      (-DLBSIM_DYN_MODE=0: step, 1: reset, 2: the next-step auto-reset step)
 //   lbsim_obs.hip      observe_kernel launchers
@@ -27,6 +30,7 @@
 #include "lbsim_delay.h"
 #include "lbsim_kernels.h"
 #include "lbsim_plan.h"
+#include "lbsim_pool.h"
 #include "lbsim_workers.h"
 
 namespace lbk {
@@ -90,6 +94,18 @@ void launch_dynamics_delay_step(const LaunchCtx& L, const void* action, int dtyp
                                 int32_t* assign, const uint8_t* mask, hipStream_t s);
 void launch_dynamics_delay_step_nr(const LaunchCtx& L, const void* action, int dtype,
                                    int32_t* assign, const uint8_t* mask, hipStream_t s);
+
+// The dynamics of a handle with shared server pools (lbsim_dyn_pool.hip: dynamics_pool_kernel; the
+// plan is a pool one and pa holds the physical FIFOs).  A reset's mask is the widened one.
+void launch_dynamics_pool_step(const LaunchCtx& L, const PoolArrays& pa, const void* action,
+                               int dtype, int32_t* assign, hipStream_t s);
+void launch_dynamics_pool_reset(const LaunchCtx& L, const PoolArrays& pa, const uint8_t* mask,
+                                hipStream_t s);
+// pa.mask[b] = whether any member of env b's pool is in `mask` (B bytes, non-NULL).
+void launch_pool_mask(const PoolArrays& pa, const uint8_t* mask, int B, hipStream_t s);
+// lbsim_ground_truth of a pool handle: the physical servers' rows; mu: the config's rates.
+void launch_pool_truth(const LaunchCtx& L, const PoolArrays& pa, const float* mu, float* out,
+                       hipStream_t s);
 
 void launch_observe_step(const LaunchCtx& L, const ObsOutputs& o, const uint8_t* mask,
                          hipStream_t s);

@@ -3,7 +3,7 @@
 // fixed by then) and keeps the StepPlan in the handle; lbsim_dynamics_kernel, lbsim_step_ex and
 // lbsim_reset_ex read it, the launchers (lbsim_dyn.hip, lbsim_obs.hip, lbsim_step.hip) turn it
 // into template arguments.  What a call decides stays with the call: facade outputs, the reset
-// mask, step vs reset.  Plain host C++17 with no HIP header: tests/plan_probe.cpp compiles it alone
+// mask, step vs reset.  Plain host C++17 with no HIP header (lbsim_pool.h is one too): tests/plan_probe.cpp compiles it alone
 // and tests/test_step_plan.py checks it against tests/golden/step_plan.jsonl without a GPU.
 #pragma once
 #include <cstdint>
@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "../../include/lbsim.h"
+#include "lbsim_pool.h"
 
 namespace lbk {
 
@@ -63,6 +64,7 @@ struct PlanInput {
   bool cross_traffic = false;  // hidden cross traffic is on (lbsim_cross_traffic_enable)
   bool server_workers = false;  // multi-worker servers are on (lbsim_server_workers_enable)
   bool action_delay = false;  // action latency is on (lbsim_action_delay_enable)
+  int pool = 0;  // balancers per shared server pool (lbsim_server_pool_enable); 0: no pools
 };
 
 enum StepForm { kStepWave, kStepGroupFused, kStepTwoLaunch };
@@ -78,8 +80,9 @@ constexpr int kObserveSplitS = 16;
 constexpr unsigned env_lane_block(int maxs) { return maxs <= 8 ? 256u : 128u; }
 
 struct DynPlan {
-  int kernel;   // lbsim_dyn_kernel: LBSIM_DYN_KERNEL_ENV_LANE | _GROUP | _WAVE
-  int width;    // env-lane: MAXS 4 | 8 | 16; group: G lanes per env; wave: NG ring registers
+  int kernel;   // lbsim_dyn_kernel: LBSIM_DYN_KERNEL_ENV_LANE | _GROUP | _WAVE | _POOL
+  int width;    // env-lane: MAXS 4 | 8 | 16; group: G lanes per env; wave: NG ring registers;
+                // pool: G lanes per pool
   bool full;    // group: dynamics_group_full_kernel (every feature's code, its own budget)
   int waves;    // group, not full: the WAVES register budget 1 | 4 | 5
   int epw;      // group: envs per wave
@@ -125,7 +128,11 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
   // Action latency: so are the weight ring and the mid-step switch.
   const bool full_only = in.res_vpp || in.flow_stats || in.work_tables || in.cross_traffic ||
                          in.server_workers || in.action_delay;
-  const bool wave_fits = ov.dyn_wave != 0 && !ov.group_lanes_set &&
+  // Shared server pools: dynamics_pool_kernel for step and reset, one group of
+  // pow2 >= max(S, A) lanes per pool (LBSIM_DYN_GROUP_LANES = 4 | 8 | 16 where it holds both), and
+  // the ordinary two-launch observe: no wave kernel, no one-launch step.
+  const bool pool = in.pool > 0;
+  const bool wave_fits = !pool && ov.dyn_wave != 0 && !ov.group_lanes_set &&
                          in.dyn_mapping != LBSIM_DYN_ENV_PER_LANE && S <= 8 && in.Q <= 32 &&
                          in.policy != LBSIM_POLICY_ALIAS && !in.fail && !in.leak && !in.split &&
                          !full_only;
@@ -164,7 +171,10 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
 
   const auto dynamics = [&](bool step) {
     DynPlan d{};
-    if (wave_ok) {
+    if (pool) {
+      const int pg = pool_group_lanes(S, in.pool, fl);
+      d = {LBSIM_DYN_KERNEL_POOL, pg, false, 0, 64 / pg, blocks(B / in.pool, 64 / pg), 64u};
+    } else if (wave_ok) {
       d = {LBSIM_DYN_KERNEL_WAVE, ng, false, 0, 0, (unsigned)B, 64u};
     } else if (g == 0) {
       const int maxs = S <= 4 ? 4 : S <= 8 ? 8 : 16;
@@ -211,7 +221,7 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
     p.occ = occ2 ? 2 : 4;
     p.obs_maxs = ng == 4 ? 8 : kObsChunkServers;  // S = 5-8: both chunks
     p.grid = (unsigned)B;
-  } else if (k == LBSIM_STEP_FUSED && !in.next_reset && !full && g >= 2 && g <= 16) {
+  } else if (k == LBSIM_STEP_FUSED && !pool && !in.next_reset && !full && g >= 2 && g <= 16) {
     // The group-fused step is opt-in (AUTO = SPLIT: it measured slower at every shape tried,
     // DESIGN.md §5), not for full handles, and has no form for S > 16 or one lane per env.  It
     // runs 64 / G envs per wave whatever LBSIM_DYN_EPW says.

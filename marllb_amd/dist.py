@@ -7,6 +7,9 @@ reductions of the per-rank results.  Weak scaling: per-rank B is fixed as world 
 Per-env rates (VecLoadBalanceEnv.set_rates) shard the same way: a rank passes its own rows,
 arrays[lo:hi] of the global (B,) / (B, S) arrays; so do rate schedules and trace ids
 (set_rate_schedule, set_env_trace, set_trace_schedule): Shard.rows(x) is a rank's slice.
+Shared server pools (balancers_per_pool = A) shard by whole pools: envs_per_rank
+must be a multiple of A, so every env_id_offset is one too (pool_shard builds such a Shard from a
+pool count, Shard.check_pools verifies one).
 """
 import os
 from dataclasses import dataclass
@@ -36,6 +39,27 @@ class Shard:
             raise ValueError(f"expected {self.global_envs} rows, one per env of the whole batch "
                              f"(got {len(x)})")
         return x[self.env_id_offset:self.env_id_offset + self.envs_per_rank]
+
+    def check_pools(self, balancers_per_pool: int) -> "Shard":
+        """This shard, if it keeps pools of `balancers_per_pool` envs whole (ValueError if not)."""
+        A = int(balancers_per_pool)
+        if A < 1 or self.envs_per_rank % A != 0:
+            raise ValueError(f"envs_per_rank = {self.envs_per_rank} is no multiple of "
+                             f"balancers_per_pool = {A}: a pool would straddle two ranks")
+        return self
+
+    def pools(self, balancers_per_pool: int):
+        """The global pool ids this rank owns."""
+        A = int(balancers_per_pool)
+        self.check_pools(A)
+        return range(self.env_id_offset // A, (self.env_id_offset + self.envs_per_rank) // A)
+
+
+def pool_shard(rank: int, world: int, pools_per_rank: int, balancers_per_pool: int) -> Shard:
+    """The Shard of a rank that owns pools_per_rank whole pools of balancers_per_pool envs."""
+    if int(pools_per_rank) < 1 or int(balancers_per_pool) < 1:
+        raise ValueError("pools_per_rank and balancers_per_pool must be >= 1")
+    return Shard(int(rank), int(world), int(pools_per_rank) * int(balancers_per_pool))
 
 
 def from_env(envs_per_rank: int) -> Shard:

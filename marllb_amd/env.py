@@ -520,6 +520,15 @@ class Handle:
         """Every count 1 (lbsim_clear_server_workers), on the current stream."""
         self.check(self.lib.lbsim_clear_server_workers(self.h, ctypes.c_void_p(self._stream())))
 
+    def enable_server_pool(self, balancers: int) -> None:
+        """Shared server pools from now on (lbsim_server_pool_enable): `balancers` consecutive
+        envs share one physical set of servers; before the handle's first reset."""
+        self.check(self.lib.lbsim_server_pool_enable(self.h, int(balancers)))
+
+    def server_pool_size(self) -> int:
+        """Balancers per pool, 0 on a handle without pools (lbsim_server_pool_size)."""
+        return int(self.lib.lbsim_server_pool_size(self.h))
+
     def enable_action_delay(self, max_delay_steps: int = 1) -> None:
         """Action latency from now on (lbsim_action_delay_enable): before the handle's first
         reset, max_delay_steps in [1, 8] (ValueError otherwise)."""
@@ -683,6 +692,16 @@ class VecLoadBalanceEnv:
     passed to, inside the step where the delay is no whole number of intervals, and until then
     the previous actions' weights (1.0 before the episode's first) keep routing flows (DESIGN.md
     §3.19).  Composes with every other option; a full-kernel env as well.
+    balancers_per_pool=A makes every A consecutive envs a pool of A balancers in front of ONE
+    physical set of servers: each env keeps its own arrival stream, action row,
+    observation, reward and reservoirs, and sees in column 0 only the flows it forwarded itself,
+    while queueing, drops at full servers and completion times follow the shared FIFOs.  Shapes
+    are unchanged; a reset of any member resets its whole pool.  A must divide num_envs and
+    env_id_offset (ValueError); not with the other opt-in options, ALIAS, traces, lost FINs,
+    failures, the VPP modes, duration_mode="service" or next-step resets (LbsimError, code
+    ENOTSUP; marllb_amd.pools.check_pool_config states the rule).  set_rates(arrival_rate=...)
+    gives the members unequal shares of the traffic.  marllb_amd.VecServerPoolEnv is the (pools,
+    balancers, servers) view of such an env.
     """
 
     def __init__(self, num_envs: int, num_servers: int = 4, *, device=None,
@@ -691,7 +710,7 @@ class VecLoadBalanceEnv:
                  graph_mode: bool = False, autoreset_mode: str = "same_step",
                  flow_stats: bool = False, server_availability: bool = False,
                  cross_traffic: bool = False, server_workers=False, action_delay=False,
-                 max_delay_steps: int = 1, **kwargs):
+                 max_delay_steps: int = 1, balancers_per_pool: int = 0, **kwargs):
         torch = _torch()
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError(f"Unknown autoreset_mode: {autoreset_mode}")
@@ -714,9 +733,16 @@ class VecLoadBalanceEnv:
         self._up_buf = None
         self._up_decay = float(kwargs.get("decay_factor", 0.9))  # RES_DECAY, a Python float
         self._up_ret = None  # episode returns of the upstream reward
+        self.balancers_per_pool = int(balancers_per_pool or 0)
+        self.cfg = make_config(num_envs, num_servers, **kwargs)
+        if self.balancers_per_pool:  # the pool rule on the config, before any device is touched
+            from .pools import check_pool_config
+            check_pool_config(self.cfg, self.balancers_per_pool, flow_stats=flow_stats,
+                              server_availability=server_availability, cross_traffic=cross_traffic,
+                              server_workers=server_workers is not False and server_workers is not None,
+                              action_delay=action_delay is not False and action_delay is not None)
         self.device_index = _device_index(device)
         self.device = torch.device("cuda", self.device_index)
-        self.cfg = make_config(num_envs, num_servers, **kwargs)
         self.trace = kwargs.get("trace")
         self.num_envs = int(num_envs)
         self.num_servers = int(num_servers)
@@ -725,6 +751,8 @@ class VecLoadBalanceEnv:
         self.keep_terminal_obs = keep_terminal_obs
         self.strict_actions = strict_actions
         self.handle = Handle(self.cfg, self.device_index)
+        if self.balancers_per_pool:
+            self.handle.enable_server_pool(self.balancers_per_pool)
         if flow_stats:
             self.handle.enable_flow_stats()
         self.server_availability = bool(server_availability)
@@ -804,7 +832,14 @@ class VecLoadBalanceEnv:
         if m.numel() != self.num_envs:
             raise ValueError(f"reset mask must have num_envs={self.num_envs} entries, "
                              f"got {m.numel()}")
-        return m.reshape(-1).to(self.device).to(torch.uint8).contiguous()
+        m = m.reshape(-1).to(self.device).to(torch.uint8)
+        # a pool resets iff any member's entry is set, and whole.  The library widens the mask it is
+        # given for its own launches; this copy is what the host-side bookkeeping of a masked
+        # reset reads (feature_mode="upstream" rows, the upstream returns)
+        if self.balancers_per_pool > 1:
+            A = self.balancers_per_pool
+            m = m.view(-1, A).amax(1, keepdim=True).expand(-1, A).reshape(-1)
+        return m.contiguous()
 
     def _upstream(self, obs, reward=None, rows=None):
         """Overwrite obs[:, :, 1:] (and reward) with the upstream features of the current state;

@@ -324,3 +324,34 @@ def sample_action_delay(num_envs: int, low: float = 0.0, high: float = 0.25, see
     # microsecond that the conversion to whole us rounds away)
     d = (lo + (hi - lo) * u).clamp(0.0, top)
     return d.to(device=device, dtype=torch.float32).contiguous()
+
+
+def sample_pool_arrival_rates(num_pools: int, num_balancers: int, total=(200.0, 400.0),
+                              skew=(1.0, 1.0), seed: int = 0, *, generator=None, device=None):
+    """-> (num_pools * num_balancers,) float32 flows/s for set_rates(arrival_rate=...) of an env
+    with balancers_per_pool = num_balancers: the ECMP split of each pool's
+    traffic.  A pool's total rate is uniform over `total` = (lo, hi); its members' shares are a
+    geometric ladder 1, 1/q, 1/q^2, ... with q uniform over `skew` = (lo >= 1, hi), in a random
+    order, scaled to sum to the total (q = 1: equal shares).  Every rate must stay inside the
+    config's range [0.1, 1e6].  Deterministic for a seed or a seeded generator."""
+    import torch
+
+    C, A = int(num_pools), int(num_balancers)
+    if C < 1 or A < 1:
+        raise ValueError(f"need num_pools >= 1 and num_balancers >= 1 (got {num_pools}, "
+                         f"{num_balancers})")
+    tlo, thi = (float(x) for x in total)
+    qlo, qhi = (float(x) for x in skew)
+    if not (0.0 < tlo <= thi) or thi == float("inf"):
+        raise ValueError(f"total: need 0 < lo <= hi, finite (got {total})")
+    if not (1.0 <= qlo <= qhi) or qhi == float("inf"):
+        raise ValueError(f"skew: need 1 <= lo <= hi, finite (got {skew})")
+    g = generator if generator is not None else torch.Generator().manual_seed(int(seed))
+    tot = tlo + (thi - tlo) * torch.rand(C, generator=g, dtype=torch.float64)
+    q = qlo + (qhi - qlo) * torch.rand(C, generator=g, dtype=torch.float64)
+    order = torch.rand(C, A, generator=g, dtype=torch.float64).argsort(dim=1)
+    share = q.unsqueeze(1) ** (-order.to(torch.float64))
+    rates = tot.unsqueeze(1) * share / share.sum(dim=1, keepdim=True)
+    if float(rates.min()) < 0.1 or float(rates.max()) > 1.0e6:
+        raise ValueError("a member's rate leaves [0.1, 1e6] flows/s: narrow `total` or `skew`")
+    return rates.reshape(-1).to(device=device, dtype=torch.float32).contiguous()
