@@ -8,9 +8,12 @@
 // layout as dynamics_kernel, so the two mappings are interchangeable between
 // launches and bit-identical to the oracle.
 //
-// Arrival-driven like dynamics_kernel's sim_step: each iteration, every lane pops its own server's
-// head if it completed by the next arrival (a group with a second due pop spends one more
-// iteration), then the group assigns the arrival:
+// Arrival-driven like dynamics_kernel's sim_step.  A plain handle (in groups of 4 lanes and more)
+// spends one iteration per arrival and counts each server's queue by completion time
+// (group_count_loop); a full or delay handle, whose features need every pop as an event, and the
+// 2-lane groups (see sim_step_group) pop: each iteration, every lane pops its own
+// server's head if it completed by the next arrival, a group with a second due pop spending one
+// more iteration (group_event_loop).  Then, in both, the group assigns the arrival:
 //   SED / LSQ choice: the reference's scan "start at the hashed server h, replace on a strictly
 //     lower score" equals: h (or the first eligible server when h is full) if its score is the
 //     minimum or NaN, else the lowest eligible server holding the minimum — with finite scores a
@@ -640,6 +643,236 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
   }
 }
 
+// A window slot that holds no queued entry (dynamics_wave_kernel's marker): below every arrival
+// time, so the slot never counts as queued.
+constexpr int32_t kGroupFree = -(1 << 30);
+
+// The event loop of a plain handle (section 2 of sim_step_group; the full and the delay handles
+// keep group_event_loop, whose features need each pop as an event): one iteration per ARRIVAL, and
+// the queue counted by time instead of popped.  A FIFO server fixes a flow's completion time when
+// the flow is queued, and the times increase strictly along a queue (tc = max(tail, ta) + svc,
+// svc >= 1), so the flows queued at time t are the entries with tc > t: nothing has to be popped
+// to know their number, no iteration is spent on a second due pop, and the eight window times sit
+// at addresses fixed for the step (no head index between one iteration's read and the next).
+// The lane's window slots hold, in circular order ending at wpos - 1, the latest entries that went
+// through the window; the completed ones among them (tc <= t) and the free slots (kGroupFree) do
+// not count.  nring entries wait past the window in the HBM ring, all later than the window's.
+// FAST as in group_event_loop: the two forms differ only in how they choose.
+template <int G, int POLICY, bool TRACE, bool FAST>
+__device__ __forceinline__ void group_count_loop(const DevState& st, const SimParams& p,
+                                                 LaneState<1>& E, SrvLane& V, int s, int gbase,
+                                                 int n_alias, const GroupConst& gc, int2* win,
+                                                 int32_t* atab, int4* acache, uint2* const my_res,
+                                                 int2* const my_ring,
+                                                 const TraceSel& ts = TraceSel{}) {
+  constexpr int WL = kGroupWL;
+  constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
+  constexpr bool alias = POLICY == kPolicyAlias;
+  constexpr bool lsq = (POLICY == 2 || POLICY == 3);
+  const int S = p.S, Q = p.Q;
+  const int32_t dt = gc.dt;
+  const GroupAliasTab tab{atab, gbase};
+  const int lane = gbase + s;
+  auto wslot = [&](int i) -> int2* { return win + i * 64 + lane; };
+  auto mark = [&](int slot) {  // the slot's bit in the lane's 128-bit written-slot mask
+    atomicOr(V.chgw + ((uint32_t)slot >> 5) * 64u, 1u << (slot & 31));
+  };
+  // ---- entry: the window slots outside the queued run get the free marker (LDS is not
+  //      initialised, and an entry popped in an earlier step kept its time of that step's clock)
+  const int nw0 = V.cnt < WL ? V.cnt : WL;
+#pragma unroll
+  for (int i = 0; i < WL; ++i)
+    if (i >= nw0) wslot((V.lh + i) & (WL - 1))->x = kGroupFree;
+  int nring = V.cnt - nw0;              // entries past the window
+  int wpos = (V.lh + nw0) & (WL - 1);   // the next window slot
+  int pidx = V.head + V.cnt;            // the ring index of the next push (every push steps it: the
+  pidx = pidx >= Q ? pidx - Q : pidx;   // window's entries have their ring places too); the first
+                                        // entry past the window is nring places before it
+  int32_t lastdone = V.last;            // the latest completion by dt so far
+  // The window's entries queued at time t, by their times (the ring's are all queued: they are
+  // later than the window's).  Rare: while the ring holds entries and the window fewer than WL
+  // queued ones, the oldest ring entry moves into the next window slot (free: the queued ones are
+  // the run of n_win slots ending at wpos - 1).  Afterwards the ring part is empty or the window
+  // holds WL queued entries, which are then the first WL of the queue.  The inner loop ends: every
+  // trip takes one entry from nring.
+  // (The compare-and-add as (t - x) >> 31, to keep the count off VCC, comes back from the
+  // compiler as the same v_cmp / v_addc pairs: profiles/dyn_count/.)
+  auto count_at = [&](int32_t t) -> int {
+    int n_win = 0;
+#pragma unroll
+    for (int k = 0; k < WL; ++k) n_win += wslot(k)->x > t ? 1 : 0;
+    while (nring > 0 && n_win < WL) {
+      int ri = pidx - nring;  // the oldest ring entry's place
+      ri = ri < 0 ? ri + Q : ri;
+      const int2 e = my_ring[(uint32_t)ri];
+      __builtin_amdgcn_s_waitcnt(kWaitVmcnt0);  // (no flat access: see dynamics_kernel)
+      *wslot(wpos) = e;
+      wpos = (wpos + 1) & (WL - 1);
+      nring -= 1;
+      n_win += e.x > t ? 1 : 0;
+    }
+    return n_win;
+  };
+  // Draw-ahead as in group_event_loop: every G iterations (= arrivals) lane j of a group draws
+  // arrival cbase + j into the group's slots acache[gbase + j].
+  uint32_t cbase = 0u;
+  uint32_t it = 0u;
+  uint32_t kbase = E.arr_idx + 1u, rbase = 0u;
+  if constexpr (TRACE) rbase = trace_row_in(ts.rows, E.gid, E.episode, kbase);
+  // One arrival per iteration (the same in every lane of the group), so the loop ends with the
+  // step's arrivals; its last pass only counts, at dt.  One copy of the count's code serves the
+  // arrivals and the step's end: as `while (next_arr < dt)` with a second count after it, the
+  // reset kernels of LSQ trace handles took a 68-byte private segment (profiles/dyn_count/).
+  int n_end;
+  for (;;) {
+    const bool arrival = E.next_arr < dt;
+    const int32_t ta = arrival ? E.next_arr : dt;
+    const int n_win = count_at(ta);
+    if (!arrival) {
+      n_end = n_win;
+      break;
+    }
+    if ((it & (uint32_t)(G - 1)) == 0u) {
+      cbase = E.arr_idx + 1u;
+      const uint32_t k = cbase + (uint32_t)s;
+      uint32_t rk0[10], rk1[10];
+      const uint32_t k0 = gc.k0, k1 = gc.k1;
+#pragma unroll
+      for (int r = 0; r < 10; ++r) {
+        rk0[r] = k0 + (uint32_t)r * 0x9E3779B9u;
+        rk1[r] = k1 + (uint32_t)r * 0xBB67AE85u;
+      }
+      const u32x4 d = philox_rk(u32x4{k, E.gid, E.episode, kStreamArrival << 24}, rk0, rk1);
+      int32_t gap;
+      float wk;
+      if constexpr (TRACE) {
+        const uint32_t rows = ts.rows;  // the env's own trace: rows [base, base + rows)
+        rbase += cbase - kbase;  // <= G arrivals since the last refill
+        kbase = cbase;
+        while (rbase >= rows) rbase -= rows;
+        uint32_t r = rbase + (uint32_t)s;
+        while (r >= rows) r -= rows;
+        gap = (int32_t)st.trace_gap[ts.base + r];
+        wk = st.trace_work[ts.base + r];
+      } else {
+        gap = (int32_t)(-lb_logf(u01_open0(d.x)) * gc.mean_gap);
+        wk = -lb_logf(u01_open0(d.y));
+      }
+      acache[lane] = make_int4(gap, __float_as_int(wk), (int)d.z, (int)d.w);
+      __builtin_amdgcn_wave_barrier();
+    }
+    // the next arrival's words: read now, used at the iteration's end
+    const int4 nx = acache[gbase + (int)(E.arr_idx + 1u - cbase)];
+    ++it;
+    const int n = n_win + nring;  // the server's queue at ta
+
+    // ---- the arrival: choose a server (node.c:388-441); full servers are not eligible
+    if constexpr (!alias) {
+      if constexpr (lsq) {
+        V.score = (float)n;
+      } else {  // (n + 1) / den correctly rounded (Markstein), division for den 0 / inf / NaN
+        const double c = (double)(n + 1);
+        const double q0 = c * V.rcp;
+        double q = fma(fma(-q0, V.den, c), V.rcp, q0);
+        if (!FAST && q != q) {
+          asm volatile("");
+          q = c / V.den;
+        }
+        V.score = (float)q;
+      }
+    }
+    const bool elig = V.act && n < V.qcap;
+    int chosen = -1;
+    if constexpr (alias) {
+      const uint64_t em = group_bits<G>(__ballot(elig), gbase);
+      if (n_alias > 0) {
+        const int a = alias_pick(tab, n_alias, E.u2);
+        chosen = ((em >> a) & 1u) ? a : -1;
+      }
+    } else if constexpr (two_choice) {
+      const uint64_t em = group_bits<G>(__ballot(elig), gbase);
+      const int h1 = two_choice_h1(E.u2, S);
+      const int h2 = two_choice_h2(E.u2, S);
+      const uint32_t bits = __float_as_uint(V.score);
+      const float s1 = __uint_as_float(group_or<G>(s == h1 ? bits : 0u));
+      const float s2 = __uint_as_float(group_or<G>(s == h2 ? bits : 0u));
+      const bool ok1 = (em >> h1) & 1u, ok2 = (em >> h2) & 1u;
+      chosen = (ok1 && ok2) ? ((s2 < s1) ? h2 : h1) : (ok1 ? h1 : (ok2 ? h2 : -1));
+    } else if constexpr (FAST) {
+      // finite scores: a lexicographic (score, rank) minimum, rank 0 for h and s + 1 otherwise, as
+      // two DPP min reductions (see group_event_loop)
+      const int32_t key = elig ? f32_key(V.score) : 0x7FFFFFFF;  // finite keys < 0x7f800001
+      const int32_t mk = group_min_i32<G>(key);
+      const int h = (int)__umulhi(E.u2, (uint32_t)S);
+      const int32_t rk = (elig && key == mk) ? (s == h ? 0 : s + 1) : 0xFF;
+      const int32_t mr = group_min_i32<G>(rk);
+      chosen = mr == 0xFF ? -1 : (mr == 0 ? h : mr - 1);
+    } else {
+      const uint64_t em = group_bits<G>(__ballot(elig), gbase);
+      const bool num = elig && V.score == V.score;
+      const float m = key_f32(group_min_i32<G>(num ? f32_key(V.score) : 0x7f800000));
+      const int h = (int)__umulhi(E.u2, (uint32_t)S);
+      const int c0 = ((em >> h) & 1u) ? h : (em ? __builtin_ctzll(em) : -1);
+      const uint64_t tie = group_bits<G>(__ballot(num && V.score == m), gbase);
+      const uint64_t nan = group_bits<G>(__ballot(V.score != V.score), gbase);
+      chosen = c0 < 0 ? -1 : ((((tie | nan) >> c0) & 1u) ? c0 : (tie ? __builtin_ctzll(tie) : -1));
+    }
+    E.dropped += chosen < 0 ? 1u : 0u;
+    const bool mine = s == chosen;
+
+    // ---- FIFO service on the chosen server (its lane).  No test for an empty queue: its tail
+    //      completed by ta (tail <= ta; 0 after a reset, a load or a failure), so the maximum is ta
+    const int32_t start_a = V.tail > ta ? V.tail : ta;
+    int32_t svc = (int32_t)(E.next_work * V.scale);
+    svc = svc < 1 ? 1 : svc;
+    const int32_t tc_a = start_a + svc;
+    const bool ins = mine && tc_a <= dt;  // completes in this step: its sample now
+
+    // ---- the pushed flow's Algorithm R draw is this arrival's word r (E.u3)
+    const int slot = reservoir_slot_r32(V.rcnt, E.u3);
+    if (ins && slot >= 0) {
+      const uint32_t fct = (uint32_t)(tc_a - ta);
+      my_res[(uint32_t)slot] = make_uint2(fct, gc.base_ms + (gc.base_rem + (uint32_t)tc_a) / 1000u);
+      mark(slot);
+    }
+    if (mine) {
+      const int2 e = make_int2(tc_a, ta);
+      if (n_win < WL) {  // (then the ring part is empty, and slot wpos is free)
+        *wslot(wpos) = e;
+        wpos = (wpos + 1) & (WL - 1);
+      } else {
+        my_ring[(uint32_t)pidx] = e;
+        asm volatile("");  // no flat store (see dynamics_kernel)
+        nring += 1;
+      }
+      pidx = pidx + 1 == Q ? 0 : pidx + 1;
+      V.tail = tc_a;
+      V.assigned += 1;
+      V.rcnt = ins ? count_inc(V.rcnt) : V.rcnt;
+      lastdone = ins ? tc_a : lastdone;
+    }
+
+    // ---- next arrival (identical in every lane of the group): arrival arr_idx + 1 from the
+    //      group's draw-ahead slots
+    E.next_arr = ta + nx.x;
+    E.next_work = __int_as_float(nx.y);
+    E.u2 = (uint32_t)nx.z;
+    E.u3 = (uint32_t)nx.w;
+    E.arr_idx += 1u;
+  }
+  // ---- the step's end: the queue at dt, the window holding its first min(cnt, WL) entries, and
+  //      the server's fields as the pop-based loop leaves them
+  V.cnt = n_end + nring;
+  int head = pidx - V.cnt;  // the ring place of the first queued entry (cnt <= Q)
+  V.head = head < 0 ? head + Q : head;
+  V.lh = (wpos - n_end) & (WL - 1);
+  V.head_tc = V.cnt > 0 ? wslot(V.lh)->x : V.head_tc;
+  // the last completion by dt: a flow pushed in this step, else a carried-in one (section 1 left
+  // it in V.last), else none new.  Not "the slot before the head": a push at WL - 1 queued
+  // entries overwrites that slot.
+  V.last = lastdone;
+}
+
 template <int G, int POLICY, bool TRACE, bool FULL = false, bool DELAY = false>
 __device__ __forceinline__ void sim_step_group(const DevState& st, const SimParams& p,
                                                LaneState<1>& E, SrvLane& V, uint32_t b, int s,
@@ -658,6 +891,11 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
   const uint32_t base_rem = (uint32_t)(base_us - (uint64_t)base_ms * 1000u);
   constexpr bool alias = POLICY == kPolicyAlias;
   constexpr bool lsq = (POLICY == 2 || POLICY == 3);
+  // The plain handles' event loop counts the queue by time (group_count_loop); the full and the
+  // delay handles pop (group_event_loop), and so do the 2-lane groups: with the counting loop the
+  // 2-lane reset kernels of trace handles took a 68-byte private segment and the 2-lane
+  // fused_step_kernel 236 VGPRs for 234 (profiles/dyn_count/), and no measured shape runs them.
+  constexpr bool COUNT = !FULL && G > 2;
   const uint32_t sb = b * (uint32_t)S + (uint32_t)s;  // valid when V.act
   uint2* const my_res = st.res + (size_t)sb * K;
   int2* const my_ring = st.ring + (size_t)sb * (size_t)Q;
@@ -688,6 +926,7 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
     E.dropped += group_add<G>(fails ? (uint32_t)V.cnt : 0u);
     if (fails) {
       V.cnt = 0;
+      if constexpr (COUNT) V.tail = 0;  // group_count_loop's start rule: an empty queue's tail <= ta
       V.last = kLastNone;
       V.rcnt = 0u;
       V.big = false;
@@ -768,6 +1007,9 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
       }
     }
     V.rcnt = rc;
+    // the last completion so far: group_count_loop pops nothing, so it starts from this value
+    // (the pop-based loop assigns V.last at every pop and never reads it: kept out of it)
+    if constexpr (COUNT) V.last = prev;
   }
 
   // ---- 2. one arrival per iteration (as dynamics_kernel's sim_step), the group in step.  SED /
@@ -784,12 +1026,19 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                                                            ts, ws, cx, wk, dl);
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
+  } else if constexpr (!COUNT) {
+    if (__all(finite))
+      group_event_loop<G, POLICY, TRACE, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
+                                               acache, my_res, my_ring, false, ts, ws);
+    else
+      group_event_loop<G, POLICY, TRACE, false>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
+                                                acache, my_res, my_ring, false, ts, ws);
   } else if (__all(finite)) {
-    group_event_loop<G, POLICY, TRACE, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                             acache, my_res, my_ring, false, ts, ws);
+    group_count_loop<G, POLICY, TRACE, true>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
+                                             acache, my_res, my_ring, ts);
   } else {
-    group_event_loop<G, POLICY, TRACE, false>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
-                                              acache, my_res, my_ring, false, ts, ws);
+    group_count_loop<G, POLICY, TRACE, false>(st, p, E, V, s, gbase, n_alias, gc, win, atab,
+                                              acache, my_res, my_ring, ts);
   }
 
   // ---- rebase to the next step's start (this lane's server)
