@@ -124,7 +124,8 @@ enum lbsim_dyn_kernel {
   LBSIM_DYN_KERNEL_ENV_LANE = 0,  /* dynamics_kernel: one lane per env                        */
   LBSIM_DYN_KERNEL_GROUP = 1,     /* dynamics_group_kernel: one lane per server, G-lane groups */
   LBSIM_DYN_KERNEL_WAVE = 2,      /* dynamics_wave_kernel: one wave per env                    */
-  LBSIM_DYN_KERNEL_POOL = 3       /* dynamics_pool_kernel: one G-lane group per server pool    */
+  LBSIM_DYN_KERNEL_POOL = 3,      /* dynamics_pool_kernel: one G-lane group per server pool    */
+  LBSIM_DYN_KERNEL_PS = 4         /* dynamics_ps_kernel: processor-sharing servers, G-lane groups */
 };
 
 /* How lbsim_step runs; every choice produces the same bits.  FUSED: one launch per step whose
@@ -856,6 +857,34 @@ int lbsim_action_delay_load(lbsim_t* h, const void* dev_buf, size_t bytes, const
  * lbsim_server_pool_size: A, or 0 on a handle that was not enabled. */
 int lbsim_server_pool_enable(lbsim_t* h, int32_t balancers);
 int lbsim_server_pool_size(const lbsim_t* h);
+
+/* Processor-sharing servers, opt-in per handle: every server has one
+ * worker that the n flows queued on it share equally, instead of serving them first come first
+ * served.  All quantities are integer us.  A server keeps a virtual clock V, a carry acc and the
+ * time t_last of its last update; advance(t): with n > 0 queued, acc += t - t_last, V += acc / n,
+ * acc %= n (else acc = 0), then t_last = t.  An arrival at ta assigned to the server advances it
+ * to ta, takes svc = max(1, (int)(work * 1e6 / mu)) as on a FIFO server and the tag V + svc, and
+ * is queued in tag order after every equal tag.  The head completes at t_last + (tag_head - V) *
+ * n - acc; its sample fct = tc - ta is stamped as every sample is and always drawn from the
+ * reservoir stream.  Everything else -- arrivals, the SED / LSQ scores on the queued counts,
+ * eligibility n < queue_capacity, drops, the pop rule (completions due no later than the next
+ * arrival first), the rebase, clock -- is the FIFO simulator's.  At a step's end every server is
+ * advanced to dt; the ring then holds {tag - V, ta - dt} in tag order and the server's last_tc
+ * word holds acc: the state layout and lbsim_state_size are those of any handle.
+ * lbsim_processor_sharing_enable: before the handle's first lbsim_reset (LBSIM_EINVAL after it; a
+ * second call is a no-op).  LBSIM_ENOTSUP, the message naming the option, with assign_policy
+ * ALIAS, arrival_source TRACE, lost_fin_prob > 0, fail_prob > 0, reservoir_mode VPP,
+ * n_flow_on_mode VPP, duration_mode SERVICE or next_step_reset, and on a handle with server
+ * availability, cross traffic, server workers, action delay or server pools; on an enabled handle
+ * those opt-ins and lbsim_ground_truth (its wait and backlog columns are FIFO quantities) return
+ * LBSIM_ENOTSUP.  Per-env rates, rate schedules, workload tables, flow statistics, masked resets,
+ * lbsim_state_save / lbsim_state_load, lbsim_get_state / lbsim_set_state, lbsim_vpp_export and
+ * hipGraph capture of lbsim_step work as on any handle.  The steps launch dynamics_ps_kernel
+ * (lbsim_dynamics_kernel: LBSIM_DYN_KERNEL_PS) and the handle's ordinary observe; no allocation
+ * or synchronisation is added to lbsim_step or lbsim_reset.
+ * lbsim_processor_sharing: 1 on an enabled handle, else 0. */
+int lbsim_processor_sharing_enable(lbsim_t* h);
+int lbsim_processor_sharing(const lbsim_t* h);
 
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/

@@ -206,6 +206,8 @@ _SIGNATURES = {
     "lbsim_action_delay_load": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
     "lbsim_server_pool_enable": (ctypes.c_int, [_P, ctypes.c_int32]),
     "lbsim_server_pool_size": (ctypes.c_int, [_P]),
+    "lbsim_processor_sharing_enable": (ctypes.c_int, [_P]),
+    "lbsim_processor_sharing": (ctypes.c_int, [_P]),
     "lbsim_server_avail_enable": (ctypes.c_int, [_P]),
     "lbsim_set_server_avail": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_int32, _P]),

@@ -135,6 +135,7 @@ struct lbsim {
   // lbsim_server_pool_enable: the physical FIFOs' words and owners (two state sections after all
   // the others, sections() below) and the widened reset mask, allocated once and never moved
   PoolArrays pool{};  // (A = 0: the handle has no pools)
+  bool ps = false;  // lbsim_processor_sharing_enable: processor-sharing servers
   bool initialised;  // a full reset has been issued
   bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
@@ -161,6 +162,10 @@ int fail(lbsim_t* h, int code, const char* fmt, ...) {
 // An opt-in refused on a handle with shared server pools (not composed).
 const char kPoolNoCompose[] = "%s on a handle with shared server pools "
                               "(lbsim_server_pool_enable): not supported together";
+
+// An opt-in refused on a handle with processor-sharing servers (not composed).
+const char kPsNoCompose[] = "%s on a handle with processor-sharing servers "
+                            "(lbsim_processor_sharing_enable): not supported together";
 
 // Scoped hipSetDevice that restores the caller's current device (torch keeps its own).
 struct DeviceGuard {
@@ -1211,6 +1216,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.server_workers = h->workers_buf != nullptr;
   in.action_delay = h->delay_buf != nullptr;
   in.pool = h->pool.A;
+  in.ps = h->ps;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -1222,6 +1228,11 @@ int launch_dynamics(lbsim_t* h, const void* action, int dtype, int32_t* assign,
     if (mode == kModeStep) launch_dynamics_pool_step(ctx(h), h->pool, action, dtype, assign, stream);
     else launch_dynamics_pool_reset(ctx(h), h->pool, mask, stream);
     return launch_check(h, "dynamics_pool_kernel");
+  }
+  if (h->ps) {  // processor-sharing servers: their own kernel
+    if (mode == kModeStep) launch_dynamics_ps_step(ctx(h), action, dtype, assign, stream);
+    else launch_dynamics_ps_reset(ctx(h), mask, stream);
+    return launch_check(h, "dynamics_ps_kernel");
   }
   if (mode == kModeStep && h->plan.nr)  // next-step auto-reset: done envs reset instead
     launch_dynamics_step_nr(ctx(h), action, dtype, assign, mask, stream);
@@ -2086,6 +2097,7 @@ int lbsim_flow_stats_enable(lbsim_t* h) {
 
 int lbsim_cross_traffic_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "cross traffic");
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "cross traffic");
   if (h->cross_buf != nullptr) return LBSIM_OK;
   if (h->prm.lf_thr != 0u)
@@ -2192,6 +2204,7 @@ int lbsim_clear_cross_traffic(lbsim_t* h, void* stream) {
 
 int lbsim_server_workers_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
+  if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "server workers");
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "server workers");
   if (h->workers_buf != nullptr) return LBSIM_OK;
   if (h->prm.lf_thr != 0u)
@@ -2281,6 +2294,10 @@ int lbsim_ground_truth(lbsim_t* h, float* truth_out, void* stream) {
     return fail(h, LBSIM_EINVAL, "ground truth: truth_out must be aligned to 16 bytes");
   if (!h->initialised)
     return fail(h, LBSIM_EINVAL, "call lbsim_reset before lbsim_ground_truth");
+  if (h->ps)
+    return fail(h, LBSIM_ENOTSUP, "lbsim_ground_truth on a handle with processor-sharing servers "
+                                  "(lbsim_processor_sharing_enable): its wait and backlog columns "
+                                  "are FIFO quantities");
   DeviceGuard g(h->device);
   if (h->pool.A > 0) {  // shared server pools: the physical servers' rows
     launch_pool_truth(ctx(h), h->pool, h->cfg.server_rate, truth_out, (hipStream_t)stream);
@@ -2341,6 +2358,7 @@ int lbsim_server_pool_enable(lbsim_t* h, int32_t balancers) {
     if (balancers == h->pool.A) return LBSIM_OK;
     return fail(h, LBSIM_EINVAL, "server pools are already on with balancers = %d", (int)h->pool.A);
   }
+  if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "server pools");
   // what the pool kernel has no code for (marllb_amd/pools.py check_pool_config states the
   // config's and the constructor's part of this list, with the same words, before a handle
   // exists: keep the two together; tests/test_server_pools.py walks both)
@@ -2392,6 +2410,41 @@ int lbsim_server_pool_enable(lbsim_t* h, int32_t balancers) {
 
 int lbsim_server_pool_size(const lbsim_t* h) { return h == nullptr ? 0 : (int)h->pool.A; }
 
+// ---- processor-sharing servers (the rule: lbsim_ps.h, the kernel:
+//      lbsim_dyn_ps.hip)
+
+int lbsim_processor_sharing_enable(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->ps) return LBSIM_OK;
+  // what the PS kernel has no code for (marllb_amd/ps.py check_ps_config states the config's and
+  // the constructor's part of this list, with the same words, before a handle exists: keep the
+  // two together; tests/test_processor_sharing.py walks both)
+  const char* no = nullptr;
+  const lbsim_config_t& c = h->cfg;
+  if (c.assign_policy == LBSIM_POLICY_ALIAS) no = "assign_policy ALIAS";
+  else if (c.arrival_source == LBSIM_ARRIVAL_TRACE) no = "arrival_source TRACE";
+  else if (c.lost_fin_prob > 0.0f) no = "lost_fin_prob > 0";
+  else if (c.fail_prob > 0.0f) no = "fail_prob > 0";
+  else if (c.reservoir_mode == LBSIM_RESERVOIR_VPP) no = "reservoir_mode VPP";
+  else if (c.n_flow_on_mode == LBSIM_NFLOW_VPP) no = "n_flow_on_mode VPP";
+  else if (c.duration_mode == LBSIM_DURATION_SERVICE) no = "duration_mode SERVICE";
+  else if (c.next_step_reset != 0) no = "next_step_reset";
+  else if (h->avail_on) no = "server availability";
+  else if (h->cross_buf != nullptr) no = "cross traffic";
+  else if (h->workers_buf != nullptr) no = "server workers";
+  else if (h->delay_buf != nullptr) no = "action delay";
+  else if (h->pool.A > 0) no = "server pools";
+  if (no != nullptr) return fail(h, LBSIM_ENOTSUP, "processor sharing with %s: not supported", no);
+  if (h->reset_seen)
+    return fail(h, LBSIM_EINVAL, "lbsim_processor_sharing_enable must precede the handle's first "
+                                 "lbsim_reset (it changes which kernels the handle launches)");
+  h->ps = true;
+  h->plan = plan_of(h);  // the PS dynamics and the two-launch paired observe (make_plan)
+  return LBSIM_OK;
+}
+
+int lbsim_processor_sharing(const lbsim_t* h) { return h != nullptr && h->ps ? 1 : 0; }
+
 // ---- action latency (the rule and the kernels: lbsim_delay.h)
 namespace {
 const char kDelayOff[] = "action delay is off: call lbsim_action_delay_enable first";
@@ -2424,6 +2477,7 @@ int delay_gather(lbsim_t* h, const char* who, void* dev_buf, size_t bytes, const
 int lbsim_action_delay_enable(lbsim_t* h, int32_t max_delay_steps) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "action delay");
+  if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "action delay");
   if (!delay_steps_ok(max_delay_steps))
     return fail(h, LBSIM_EINVAL, "action delay: max_delay_steps must be in [1, %d] (got %d)",
                 (int)kMaxDelaySteps, (int)max_delay_steps);
@@ -2526,6 +2580,7 @@ int lbsim_action_delay_load(lbsim_t* h, const void* dev_buf, size_t bytes, const
 int lbsim_server_avail_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "server availability");
+  if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "server availability");
   if (h->avail_on) return LBSIM_OK;
   if (h->prm.fail_thr != 0u)
     return fail(h, LBSIM_ENOTSUP, "scripted availability on a handle with random failures "

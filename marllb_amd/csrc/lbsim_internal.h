@@ -11,6 +11,9 @@
 //   lbsim_pool.h       shared server pools: the host / device rule of a pool and its physical FIFOs
 //   lbsim_dyn_pool.hip  dynamics_pool_kernel launchers (shared server pools); built twice
 //                      (-DLBSIM_DYN_MODE=0 step, 1 reset, with the pool handle's two small kernels)
+//   lbsim_ps.h         processor-sharing servers: the host / device rule of a server's virtual clock
+//   lbsim_dyn_ps.hip   dynamics_ps_kernel launchers (processor sharing); built twice
+//                      (-DLBSIM_DYN_MODE=0 step, 1 reset)
 //   lbsim_dyn.hip      dynamics_kernel / dynamics_group_kernel launchers; built three times
 //                      (-DLBSIM_DYN_MODE=0: step, 1: reset, 2: the next-step auto-reset step)
 //   lbsim_obs.hip      observe_kernel launchers
@@ -106,6 +109,12 @@ void launch_pool_mask(const PoolArrays& pa, const uint8_t* mask, int B, hipStrea
 // lbsim_ground_truth of a pool handle: the physical servers' rows; mu: the config's rates.
 void launch_pool_truth(const LaunchCtx& L, const PoolArrays& pa, const float* mu, float* out,
                        hipStream_t s);
+
+// The dynamics of a handle with processor-sharing servers (lbsim_dyn_ps.hip: dynamics_ps_kernel;
+// the plan is a PS one, L.flow holds the flow statistics' arrays or null pointers).
+void launch_dynamics_ps_step(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
+                             hipStream_t s);
+void launch_dynamics_ps_reset(const LaunchCtx& L, const uint8_t* mask, hipStream_t s);
 
 void launch_observe_step(const LaunchCtx& L, const ObsOutputs& o, const uint8_t* mask,
                          hipStream_t s);

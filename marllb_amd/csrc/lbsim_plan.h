@@ -65,6 +65,7 @@ struct PlanInput {
   bool server_workers = false;  // multi-worker servers are on (lbsim_server_workers_enable)
   bool action_delay = false;  // action latency is on (lbsim_action_delay_enable)
   int pool = 0;  // balancers per shared server pool (lbsim_server_pool_enable); 0: no pools
+  bool ps = false;  // processor-sharing servers (lbsim_processor_sharing_enable)
 };
 
 enum StepForm { kStepWave, kStepGroupFused, kStepTwoLaunch };
@@ -80,9 +81,9 @@ constexpr int kObserveSplitS = 16;
 constexpr unsigned env_lane_block(int maxs) { return maxs <= 8 ? 256u : 128u; }
 
 struct DynPlan {
-  int kernel;   // lbsim_dyn_kernel: LBSIM_DYN_KERNEL_ENV_LANE | _GROUP | _WAVE | _POOL
+  int kernel;   // lbsim_dyn_kernel: LBSIM_DYN_KERNEL_ENV_LANE | _GROUP | _WAVE | _POOL | _PS
   int width;    // env-lane: MAXS 4 | 8 | 16; group: G lanes per env; wave: NG ring registers;
-                // pool: G lanes per pool
+                // pool: G lanes per pool; ps: G lanes per env
   bool full;    // group: dynamics_group_full_kernel (every feature's code, its own budget)
   int waves;    // group, not full: the WAVES register budget 1 | 4 | 5
   int epw;      // group: envs per wave
@@ -132,7 +133,12 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
   // pow2 >= max(S, A) lanes per pool (LBSIM_DYN_GROUP_LANES = 4 | 8 | 16 where it holds both), and
   // the ordinary two-launch observe: no wave kernel, no one-launch step.
   const bool pool = in.pool > 0;
-  const bool wave_fits = !pool && ov.dyn_wave != 0 && !ov.group_lanes_set &&
+  // Processor-sharing servers: dynamics_ps_kernel for step and reset, one group
+  // of pow2 >= S lanes per env (LBSIM_DYN_GROUP_LANES forces the width as for the FIFO groups), and
+  // the ordinary two-launch paired observe: no wave kernel, no env-per-lane kernel, no one-launch
+  // step.
+  const bool ps = in.ps;
+  const bool wave_fits = !pool && !ps && ov.dyn_wave != 0 && !ov.group_lanes_set &&
                          in.dyn_mapping != LBSIM_DYN_ENV_PER_LANE && S <= 8 && in.Q <= 32 &&
                          in.policy != LBSIM_POLICY_ALIAS && !in.fail && !in.leak && !in.split &&
                          !full_only;
@@ -174,6 +180,11 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
     if (pool) {
       const int pg = pool_group_lanes(S, in.pool, fl);
       d = {LBSIM_DYN_KERNEL_POOL, pg, false, 0, 64 / pg, blocks(B / in.pool, 64 / pg), 64u};
+    } else if (ps) {
+      int pg = 2;
+      if (fl >= S && (fl == 4 || fl == 8 || fl == 16 || fl == 32 || fl == 64)) pg = fl;
+      else while (pg < S) pg <<= 1;
+      d = {LBSIM_DYN_KERNEL_PS, pg, false, 0, 64 / pg, blocks(B, 64 / pg), 64u};
     } else if (wave_ok) {
       d = {LBSIM_DYN_KERNEL_WAVE, ng, false, 0, 0, (unsigned)B, 64u};
     } else if (g == 0) {
@@ -221,7 +232,7 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
     p.occ = occ2 ? 2 : 4;
     p.obs_maxs = ng == 4 ? 8 : kObsChunkServers;  // S = 5-8: both chunks
     p.grid = (unsigned)B;
-  } else if (k == LBSIM_STEP_FUSED && !pool && !in.next_reset && !full && g >= 2 && g <= 16) {
+  } else if (k == LBSIM_STEP_FUSED && !pool && !ps && !in.next_reset && !full && g >= 2 && g <= 16) {
     // The group-fused step is opt-in (AUTO = SPLIT: it measured slower at every shape tried,
     // DESIGN.md §5), not for full handles, and has no form for S > 16 or one lane per env.  It
     // runs 64 / G envs per wave whatever LBSIM_DYN_EPW says.

@@ -525,6 +525,16 @@ class Handle:
         envs share one physical set of servers; before the handle's first reset."""
         self.check(self.lib.lbsim_server_pool_enable(self.h, int(balancers)))
 
+    def enable_processor_sharing(self) -> None:
+        """Processor-sharing servers from now on (lbsim_processor_sharing_enable): every server's
+        one worker is shared equally by the flows queued on it.  Before the
+        handle's first reset; a second call is a no-op."""
+        self.check(self.lib.lbsim_processor_sharing_enable(self.h))
+
+    def processor_sharing(self) -> bool:
+        """Whether the handle's servers are processor-sharing ones (lbsim_processor_sharing)."""
+        return bool(self.lib.lbsim_processor_sharing(self.h))
+
     def server_pool_size(self) -> int:
         """Balancers per pool, 0 on a handle without pools (lbsim_server_pool_size)."""
         return int(self.lib.lbsim_server_pool_size(self.h))
@@ -702,6 +712,16 @@ class VecLoadBalanceEnv:
     ENOTSUP; marllb_amd.pools.check_pool_config states the rule).  set_rates(arrival_rate=...)
     gives the members unequal shares of the traffic.  marllb_amd.VecServerPoolEnv is the (pools,
     balancers, servers) view of such an env.
+
+    service_discipline="ps" makes every server a processor-sharing one: its one
+    worker is shared equally by the flows queued on it, as an application host with more worker
+    processes than cores shares its CPU, so a short flow is never stuck behind a long one and the
+    mean sojourn time no longer depends on the flow-size variance.  With per-env rates, rate
+    schedules, workload tables, flow statistics, snapshots and graphs; not with ALIAS, traces,
+    lost FINs, failures or availability, the VPP modes, duration_mode="service", next-step
+    resets, cross traffic, server workers, action delay, pools or ground_truth() (LbsimError,
+    code ENOTSUP; marllb_amd.ps.check_ps_config states the rule).  The default "fifo" runs the
+    FIFO servers' kernels untouched.
     """
 
     def __init__(self, num_envs: int, num_servers: int = 4, *, device=None,
@@ -710,8 +730,12 @@ class VecLoadBalanceEnv:
                  graph_mode: bool = False, autoreset_mode: str = "same_step",
                  flow_stats: bool = False, server_availability: bool = False,
                  cross_traffic: bool = False, server_workers=False, action_delay=False,
-                 max_delay_steps: int = 1, balancers_per_pool: int = 0, **kwargs):
+                 max_delay_steps: int = 1, balancers_per_pool: int = 0,
+                 service_discipline: str = "fifo", **kwargs):
         torch = _torch()
+        if service_discipline not in ("fifo", "ps"):
+            raise ValueError(f"Unknown service_discipline: {service_discipline}")
+        self.service_discipline = service_discipline
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError(f"Unknown autoreset_mode: {autoreset_mode}")
         if autoreset_mode == "next_step" and feature_mode == "upstream":
@@ -741,6 +765,13 @@ class VecLoadBalanceEnv:
                               server_availability=server_availability, cross_traffic=cross_traffic,
                               server_workers=server_workers is not False and server_workers is not None,
                               action_delay=action_delay is not False and action_delay is not None)
+        if service_discipline == "ps":  # the PS rule on the config, before any device is touched
+            from .ps import check_ps_config
+            check_ps_config(self.cfg, server_availability=server_availability,
+                            cross_traffic=cross_traffic,
+                            server_workers=server_workers is not False and server_workers is not None,
+                            action_delay=action_delay is not False and action_delay is not None,
+                            balancers_per_pool=self.balancers_per_pool)
         self.device_index = _device_index(device)
         self.device = torch.device("cuda", self.device_index)
         self.trace = kwargs.get("trace")
@@ -753,6 +784,8 @@ class VecLoadBalanceEnv:
         self.handle = Handle(self.cfg, self.device_index)
         if self.balancers_per_pool:
             self.handle.enable_server_pool(self.balancers_per_pool)
+        if service_discipline == "ps":
+            self.handle.enable_processor_sharing()
         if flow_stats:
             self.handle.enable_flow_stats()
         self.server_availability = bool(server_availability)
