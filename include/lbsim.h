@@ -886,6 +886,42 @@ int lbsim_server_pool_size(const lbsim_t* h);
 int lbsim_processor_sharing_enable(lbsim_t* h);
 int lbsim_processor_sharing(const lbsim_t* h);
 
+/* Cores of processor-sharing servers, on a handle with
+ * lbsim_processor_sharing_enable (LBSIM_ENOTSUP on any other): server s of env b has c = cores[b, s]
+ * cores, each of rate server_rate, and its n flows are served at rate min(1, c / n) each: with
+ * n <= c every flow has a core to itself, above c the cores are shared equally.  The rule, integer
+ * us: advance(t) with d = t - t_last: n = 0: acc = 0; 1 <= n <= c: V += d, acc = 0; n > c: acc +=
+ * c d, V += acc / n, acc %= n; then t_last = t.  The head completes at t_last + (tag_head - V) with
+ * n <= c, else at t_last + ceil(((tag_head - V) n - acc) / c) (t_last where that is not positive),
+ * where V reaches tag_head exactly and acc is left in [0, c).  c = 1 is section 3.22's rule bit for
+ * bit; c >= queue_capacity makes fct = svc for every flow.  Everything else is section 3.22's; the
+ * state layout is unchanged (acc stays in the last_tc word) and the counts are not part of it, nor
+ * of a snapshot: a shard passes its own rows.
+ * lbsim_set_ps_cores: `cores` is int32 [rows, S] on the device, rows = 1 (every env) or num_envs
+ * (LBSIM_ESHAPE otherwise).  Converted into a staging copy and validated on `stream`, and the call
+ * waits for that stream: a count outside [1, 64] returns LBSIM_EINVAL and what was in force stays.
+ * The array is allocated by the first call, which therefore precedes a graph capture, never moves
+ * afterwards and is rewritten in place: replays of a captured lbsim_step see new counts.  They
+ * apply from the next launch on (step, reset, warm-up); queued flows keep their remaining tags.
+ * Until the first call the handle launches what it launched before, with the same results.
+ * lbsim_get_ps_cores: the counts in force into cores_out, int32 [num_envs, S] on the device (all 1
+ * before the first set call), asynchronous on `stream`.
+ * lbsim_clear_ps_cores: every count 1, in place, asynchronous on `stream`.
+ * lbsim_ps_server_state: the privileged view of the servers as they stand after the last
+ * lbsim_reset or lbsim_step (LBSIM_EINVAL before the first reset) into state_out, float32
+ * [num_envs, S, LBSIM_PS_STATE_COLS] on the device, aligned to 16 bytes: column 0 the flows n on
+ * the server, 1 the busy cores min(n, c), 2 the unfinished work in seconds of one core (the sum of
+ * the remaining tags, less acc where n > c), 3 the seconds until the server is empty with no
+ * further arrival, the last completion time the rule gives over the queued entries.  With c = 1
+ * columns 2 and 3 are equal.  One kernel on `stream`, no allocation, no synchronisation: it can
+ * be captured after lbsim_step.  (lbsim_ground_truth stays refused on these handles.) */
+#define LBSIM_PS_STATE_COLS 4
+int lbsim_set_ps_cores(lbsim_t* h, const int32_t* cores, int32_t rows, void* stream);
+int lbsim_get_ps_cores(lbsim_t* h, int32_t* cores_out, void* stream);
+int lbsim_clear_ps_cores(lbsim_t* h, void* stream);
+size_t lbsim_ps_server_state_cols(void);
+int lbsim_ps_server_state(lbsim_t* h, float* state_out, void* stream);
+
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/
  * alias_table.h:82-158, alias_table_build, rebuilt by lb_rl_node.c:92-111 from the weights the

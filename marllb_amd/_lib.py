@@ -208,6 +208,11 @@ _SIGNATURES = {
     "lbsim_server_pool_size": (ctypes.c_int, [_P]),
     "lbsim_processor_sharing_enable": (ctypes.c_int, [_P]),
     "lbsim_processor_sharing": (ctypes.c_int, [_P]),
+    "lbsim_set_ps_cores": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P]),
+    "lbsim_get_ps_cores": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_clear_ps_cores": (ctypes.c_int, [_P, _P]),
+    "lbsim_ps_server_state": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_ps_server_state_cols": (ctypes.c_size_t, []),
     "lbsim_server_avail_enable": (ctypes.c_int, [_P]),
     "lbsim_set_server_avail": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_int32, _P]),

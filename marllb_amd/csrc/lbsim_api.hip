@@ -24,6 +24,7 @@
 #include "lbsim_internal.h"
 #include "lbsim_fused.h"
 #include "lbsim_nets.h"
+#include "lbsim_ps.h"
 #include "lbsim_snapshot.h"
 #include "lbsim_stateless.h"
 #include "lbsim_truth.h"
@@ -136,6 +137,10 @@ struct lbsim {
   // the others, sections() below) and the widened reset mask, allocated once and never moved
   PoolArrays pool{};  // (A = 0: the handle has no pools)
   bool ps = false;  // lbsim_processor_sharing_enable: processor-sharing servers
+  // lbsim_set_ps_cores (§3.23): one block of 32-bit words, allocated by the first call and never
+  // moved -- the live c[B*S] the PS dynamics kernel reads, its staging copy and the offender count
+  // (nullptr: never set, every server one core)
+  int32_t* ps_cores_buf = nullptr;
   bool initialised;  // a full reset has been issued
   bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
@@ -582,6 +587,35 @@ __global__ void __launch_bounds__(256) ground_truth_kernel(TruthArgs a, float* o
   float4* const o = reinterpret_cast<float4*>(out) + 2 * i;
   o[0] = make_float4(r[0], r[1], r[2], r[3]);
   o[1] = make_float4(r[4], r[5], r[6], r[7]);
+}
+
+// ---- the privileged view of processor-sharing servers (lbsim_ps_server_state, DESIGN.md §3.23;
+//      the rule: lbsim_ps.h's ps_server_state)
+struct PsStateArgs {
+  const uint32_t* hc;
+  const int2* ring;
+  const int32_t* acc;    // the last_tc words
+  const int32_t* cores;  // nullptr: one core each
+  int32_t B, S, Q;
+};
+
+// One lane per (env, server), as ground_truth_kernel: coalesced loads of the server's words, its n
+// ring entries through the clamped accessor, the row as one 16-byte store.  n, head and acc are
+// read as the dynamics prologue reads them.
+__global__ void __launch_bounds__(256) ps_state_kernel(PsStateArgs a, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)a.B * a.S) return;
+  const uint32_t hc = a.hc[i];
+  const int head = (int)(hc & kHcHead), cnt = (int)(hc >> 16);
+  const int n = cnt <= a.Q ? cnt : a.Q;
+  const int32_t c = a.cores != nullptr ? a.cores[i] : 1;
+  const int32_t w = a.acc[i];
+  const int32_t acc = (n > 0 && w > 0 && w < n) ? w : 0;
+  const TruthRing q{a.ring + (size_t)i * (size_t)a.Q, head < a.Q ? head : 0, a.Q};
+  int32_t work = 0, drain = 0;
+  ps_server_state(q, n, c, acc, work, drain);
+  reinterpret_cast<float4*>(out)[i] = make_float4((float)n, (float)(n < c ? n : c),
+                                                  truth_seconds(work), truth_seconds(drain));
 }
 
 // A trace schedule's ids (lbsim_set_trace_schedule) expanded to B rows: out[b * P + phase] =
@@ -1230,8 +1264,10 @@ int launch_dynamics(lbsim_t* h, const void* action, int dtype, int32_t* assign,
     return launch_check(h, "dynamics_pool_kernel");
   }
   if (h->ps) {  // processor-sharing servers: their own kernel
-    if (mode == kModeStep) launch_dynamics_ps_step(ctx(h), action, dtype, assign, stream);
-    else launch_dynamics_ps_reset(ctx(h), mask, stream);
+    if (mode == kModeStep)
+      launch_dynamics_ps_step(ctx(h), action, dtype, assign, h->ps_cores_buf, stream);
+    else
+      launch_dynamics_ps_reset(ctx(h), mask, h->ps_cores_buf, stream);
     return launch_check(h, "dynamics_ps_kernel");
   }
   if (mode == kModeStep && h->plan.nr)  // next-step auto-reset: done envs reset instead
@@ -1408,6 +1444,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->flow_buf) (void)hipFree(h->flow_buf);
     if (h->cross_buf) (void)hipFree(h->cross_buf);
     if (h->workers_buf) (void)hipFree(h->workers_buf);
+    if (h->ps_cores_buf) (void)hipFree(h->ps_cores_buf);
     if (h->delay_buf) (void)hipFree(h->delay_buf);
     if (h->avail_buf) (void)hipFree(h->avail_buf);
     if (h->wtab_buf) (void)hipFree(h->wtab_buf);
@@ -2444,6 +2481,119 @@ int lbsim_processor_sharing_enable(lbsim_t* h) {
 }
 
 int lbsim_processor_sharing(const lbsim_t* h) { return h != nullptr && h->ps ? 1 : 0; }
+
+// ---- cores of processor-sharing servers (the rule: lbsim_ps.h; the conversion
+//      is lbsim_workers.h's kernel: the same range, the same offender count)
+namespace {
+const char kPsCoresOff[] = "%s on a handle without processor-sharing servers: call "
+                           "lbsim_processor_sharing_enable first";
+static_assert(kMaxWorkers == 64, "a PS server has 1 to 64 cores, a FIFO one 1 to 64 workers");
+unsigned ps_cores_blocks(const lbsim_t* h) {
+  return (unsigned)(((size_t)h->B * h->S + 255) / 256);
+}
+}  // namespace
+
+int lbsim_set_ps_cores(lbsim_t* h, const int32_t* cores, int32_t rows, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_set_ps_cores");
+  if (cores == nullptr) return fail(h, LBSIM_EINVAL, "ps cores: cores is NULL");
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "ps cores: rows must be 1 or num_envs = %d (got %d)", h->B, rows);
+  DeviceGuard g(h->device);
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t BS = (size_t)h->B * h->S, words = 2 * BS + 1;
+  const bool first = h->ps_cores_buf == nullptr;
+  int32_t* live = h->ps_cores_buf;
+  if (first) {  // (the first call: before a graph capture, as §3.10's rate arrays)
+    void* p = nullptr;
+    if (hipMalloc(&p, words * 4) != hipSuccess)
+      return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", words * 4);
+    live = (int32_t*)p;
+  }
+  int32_t* const stg = live + BS;
+  uint32_t* const bad = (uint32_t*)(live + 2 * BS);
+  int rc = LBSIM_OK;
+  uint32_t nbad = 0;
+  if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess) {
+    rc = fail(h, LBSIM_EDEVICE, "ps cores: hipMemsetAsync failed");
+  } else {
+    hipLaunchKernelGGL(workers_convert_kernel, dim3(ps_cores_blocks(h)), dim3(256), 0, s, cores,
+                       (int)rows, (int64_t)BS, h->S, stg, bad);
+    rc = launch_check(h, "workers_convert_kernel");
+    if (rc == LBSIM_OK &&
+        (hipMemcpyAsync(&nbad, bad, sizeof(nbad), hipMemcpyDeviceToHost, s) != hipSuccess ||
+         hipStreamSynchronize(s) != hipSuccess))
+      rc = fail(h, LBSIM_EDEVICE, "ps cores: conversion failed");
+  }
+  if (rc == LBSIM_OK && nbad != 0u)  // what was in force stays (before the first call: one each)
+    rc = fail(h, LBSIM_EINVAL, "ps cores: %u count(s) outside [1, %d]", nbad, (int)kMaxWorkers);
+  if (rc == LBSIM_OK &&
+      hipMemcpyAsync(live, stg, BS * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    rc = fail(h, LBSIM_EDEVICE, "ps cores: device copy failed");
+  if (first) {
+    // the block is the handle's only once it holds valid counts (the copy is ordered on s before
+    // every later launch of the caller's on it, as a set call's always is)
+    if (rc == LBSIM_OK) {
+      h->ps_cores_buf = live;
+    } else {
+      (void)hipStreamSynchronize(s);
+      (void)hipFree(live);
+    }
+  }
+  return rc;
+}
+
+int lbsim_get_ps_cores(lbsim_t* h, int32_t* cores_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_get_ps_cores");
+  if (cores_out == nullptr) return fail(h, LBSIM_EINVAL, "ps cores: cores_out is NULL");
+  DeviceGuard g(h->device);
+  const size_t BS = (size_t)h->B * h->S;
+  if (h->ps_cores_buf == nullptr) {  // never set: every count 1 (no offender: bad is not touched)
+    hipLaunchKernelGGL(workers_convert_kernel, dim3(ps_cores_blocks(h)), dim3(256), 0,
+                       (hipStream_t)stream, (const int32_t*)nullptr, 1, (int64_t)BS, h->S,
+                       cores_out, (uint32_t*)nullptr);
+    return launch_check(h, "workers_convert_kernel");
+  }
+  if (hipMemcpyAsync(cores_out, h->ps_cores_buf, BS * 4, hipMemcpyDeviceToDevice,
+                     (hipStream_t)stream) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "ps cores: device copy failed");
+  return LBSIM_OK;
+}
+
+int lbsim_clear_ps_cores(lbsim_t* h, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_clear_ps_cores");
+  if (h->ps_cores_buf == nullptr) return LBSIM_OK;  // never set: one core each already
+  DeviceGuard g(h->device);
+  const size_t BS = (size_t)h->B * h->S;
+  hipLaunchKernelGGL(workers_convert_kernel, dim3(ps_cores_blocks(h)), dim3(256), 0,
+                     (hipStream_t)stream, (const int32_t*)nullptr, 1, (int64_t)BS, h->S,
+                     h->ps_cores_buf, (uint32_t*)(h->ps_cores_buf + 2 * BS));
+  return launch_check(h, "workers_convert_kernel");
+}
+
+size_t lbsim_ps_server_state_cols(void) { return (size_t)LBSIM_PS_STATE_COLS; }
+
+int lbsim_ps_server_state(lbsim_t* h, float* state_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_ps_server_state");
+  if (state_out == nullptr) return fail(h, LBSIM_EINVAL, "ps server state: state_out is NULL");
+  if (((uintptr_t)state_out & 15u) != 0u)
+    return fail(h, LBSIM_EINVAL, "ps server state: state_out must be aligned to 16 bytes");
+  if (!h->initialised)
+    return fail(h, LBSIM_EINVAL, "call lbsim_reset before lbsim_ps_server_state");
+  DeviceGuard g(h->device);
+  PsStateArgs a{};
+  a.hc = h->st.hc;
+  a.ring = h->st.ring;
+  a.acc = h->st.last_tc;
+  a.cores = h->ps_cores_buf;
+  a.B = h->B, a.S = h->S, a.Q = h->Q;
+  hipLaunchKernelGGL(ps_state_kernel, dim3(ps_cores_blocks(h)), dim3(256), 0, (hipStream_t)stream,
+                     a, state_out);
+  return launch_check(h, "ps_state_kernel");
+}
 
 // ---- action latency (the rule and the kernels: lbsim_delay.h)
 namespace {

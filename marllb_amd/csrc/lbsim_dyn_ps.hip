@@ -13,7 +13,8 @@
 // clock to the arrival and inserts the entry by its tag.  Arrivals are drawn G at a time, lane j
 // drawing arrival k + j, as dynamics_group_kernel draws them; a PS handle may have workload
 // tables, per-env rates and flow statistics, so the draws go through the table rule when the
-// handle has tables and the statistics' arrays travel as a kernel argument (§3.11).
+// handle has tables and the statistics' arrays travel as a kernel argument (§3.11), as do the
+// servers' core counts (§3.23: a null pointer until lbsim_set_ps_cores, every server one core).
 #include "lbsim_internal.h"
 #include "lbsim_dyn_group.h"
 #include "lbsim_ps.h"
@@ -42,7 +43,8 @@ struct PsRing {
 template <int G, int MODE, int POLICY>
 __global__ void __launch_bounds__(64)
     dynamics_ps_kernel(DevState st, SimParams p, const void* action, int action_dtype,
-                       int32_t* assign_out, const uint8_t* reset_mask, FlowStats fs) {
+                       int32_t* assign_out, const uint8_t* reset_mask, FlowStats fs,
+                       const int32_t* cores) {
   static_assert(G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64,
                 "group = a power of two lanes of the wave");
   static_assert(POLICY >= 0 && POLICY <= 3, "SED, SED2, LSQ, LSQ2");
@@ -81,6 +83,9 @@ __global__ void __launch_bounds__(64)
   bool big = false;
   uint32_t cw[4] = {0u, 0u, 0u, 0u};  // the reservoir slots written this launch (DevState::chg)
   float wgt = 1.0f;
+  // the server's cores (§3.23; nullptr, wave-uniform: every server has one)
+  int32_t cr = 1;
+  if (cores != nullptr) cr = cores[sb];
   // flow statistics: a step's completions count, a reset's warm-up is not the policy's doing
   const bool fs_on = MODE == kModeStep && act && fs.hist != nullptr;
   uint32_t fs_cnt = 0u, fs_max = 0u;
@@ -142,9 +147,10 @@ __global__ void __launch_bounds__(64)
       // ---- this server's completions due no later than it, each at its own time: the clock
       //      reaches the head's tag, the head leaves, its sample is drawn from the reservoir stream
       while (act && n > 0) {
-        const int32_t tc = ps_next_completion(ck, n, head_tag);
+        const PsDue due = ps_next_completion(ck, n, cr, head_tag);
+        const int32_t tc = due.tc;
         if (tc > th) break;
-        ps_complete(ck, tc, head_tag);
+        ps_complete(ck, due, head_tag);
         const int32_t ta = ring.get(0).y;
         ring.head = ring.head + 1 == Q ? 0 : ring.head + 1;
         n -= 1;
@@ -203,7 +209,7 @@ __global__ void __launch_bounds__(64)
       dropped += chosen < 0 ? 1u : 0u;
       if (act && s == chosen) {
         // the clock up to the arrival, then the entry by its tag: after every equal one
-        ps_advance(ck, n, ta);
+        ps_advance(ck, n, cr, ta);
         int32_t svc = (int32_t)(next_work * scale);
         svc = svc < 1 ? 1 : svc;
         const int32_t tag = ck.V + svc;
@@ -244,7 +250,7 @@ __global__ void __launch_bounds__(64)
     //      tags become the remaining service, V = 0; the carry stays
     next_arr -= dt;
     if (act) {
-      ps_advance(ck, n, dt);
+      ps_advance(ck, n, cr, dt);
       head_tag -= ck.V;
       ps_rebase(ring, n, ck, dt);
     }
@@ -288,12 +294,12 @@ __global__ void __launch_bounds__(64)
 }
 
 void launch_ps_t(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
-                 const uint8_t* mask, hipStream_t stream) {
+                 const uint8_t* mask, const int32_t* cores, hipStream_t stream) {
   const DynPlan& d = MODE == kModeReset ? L.plan.reset_dyn : L.plan.dyn;
   const dim3 grid(d.grid), block(d.block);
   pick<2, 4, 8, 16, 32, 64>(d.width, [&](auto GG) { pick<0, 1, 2, 3>(L.prm.policy, [&](auto P) {
     LBSIM_LAUNCH((dynamics_ps_kernel<decltype(GG)::value, MODE, decltype(P)::value>), grid, block,
-                 0, stream, L.st, L.prm, action, dtype, assign, mask, L.flow);
+                 0, stream, L.st, L.prm, action, dtype, assign, mask, L.flow, cores);
   }); });
 }
 
@@ -301,12 +307,13 @@ void launch_ps_t(const LaunchCtx& L, const void* action, int dtype, int32_t* ass
 
 #if LBSIM_DYN_MODE == 0
 void launch_dynamics_ps_step(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
-                             hipStream_t s) {
-  launch_ps_t(L, action, dtype, assign, nullptr, s);
+                             const int32_t* cores, hipStream_t s) {
+  launch_ps_t(L, action, dtype, assign, nullptr, cores, s);
 }
 #else
-void launch_dynamics_ps_reset(const LaunchCtx& L, const uint8_t* mask, hipStream_t s) {
-  launch_ps_t(L, nullptr, 0, nullptr, mask, s);
+void launch_dynamics_ps_reset(const LaunchCtx& L, const uint8_t* mask, const int32_t* cores,
+                              hipStream_t s) {
+  launch_ps_t(L, nullptr, 0, nullptr, mask, cores, s);
 }
 #endif
 

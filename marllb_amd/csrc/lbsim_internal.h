@@ -111,10 +111,12 @@ void launch_pool_truth(const LaunchCtx& L, const PoolArrays& pa, const float* mu
                        hipStream_t s);
 
 // The dynamics of a handle with processor-sharing servers (lbsim_dyn_ps.hip: dynamics_ps_kernel;
-// the plan is a PS one, L.flow holds the flow statistics' arrays or null pointers).
+// the plan is a PS one, L.flow holds the flow statistics' arrays or null pointers; cores: the
+// servers' core counts [B * S], §3.23, or nullptr: one each).
 void launch_dynamics_ps_step(const LaunchCtx& L, const void* action, int dtype, int32_t* assign,
-                             hipStream_t s);
-void launch_dynamics_ps_reset(const LaunchCtx& L, const uint8_t* mask, hipStream_t s);
+                             const int32_t* cores, hipStream_t s);
+void launch_dynamics_ps_reset(const LaunchCtx& L, const uint8_t* mask, const int32_t* cores,
+                              hipStream_t s);
 
 void launch_observe_step(const LaunchCtx& L, const ObsOutputs& o, const uint8_t* mask,
                          hipStream_t s);

@@ -41,6 +41,8 @@ FEATURE_NAMES = [
 DEFAULT_DISCRETE_WEIGHTS = [1.0, 1.5, 2.0]  # env.py:69
 
 # columns of a ground-truth row (lbsim_ground_truth)
+# columns of a processor-sharing server's privileged state (lbsim_ps_server_state)
+PS_STATE_COLUMNS = ("n", "busy_cores", "work_s", "drain_s")
 GROUND_TRUTH_COLUMNS = ("n_total", "n_hidden", "busy", "cpu", "wait_s", "backlog_s", "up",
                         "capacity")
 
@@ -535,6 +537,33 @@ class Handle:
         """Whether the handle's servers are processor-sharing ones (lbsim_processor_sharing)."""
         return bool(self.lib.lbsim_processor_sharing(self.h))
 
+    def set_ps_cores(self, cores, *, rows: int) -> None:
+        """Core counts of processor-sharing servers (lbsim_set_ps_cores): cores (rows, S) int32
+        contiguous on the handle's device, rows = 1 or B."""
+        self.check(self.lib.lbsim_set_ps_cores(
+            self.h, ctypes.c_void_p(cores.data_ptr()), int(rows),
+            ctypes.c_void_p(self._stream())))
+
+    def ps_cores(self):
+        """(B, S) int32 device tensor: the core counts in force (lbsim_get_ps_cores)."""
+        torch = _torch()
+        out = torch.empty((int(self.cfg.num_envs), int(self.cfg.num_servers)), dtype=torch.int32,
+                          device=torch.device("cuda", self.device_index))
+        self.check(self.lib.lbsim_get_ps_cores(self.h, ctypes.c_void_p(out.data_ptr()),
+                                               ctypes.c_void_p(self._stream())))
+        return out
+
+    def clear_ps_cores(self) -> None:
+        """Every count 1 (lbsim_clear_ps_cores), on the current stream."""
+        self.check(self.lib.lbsim_clear_ps_cores(self.h, ctypes.c_void_p(self._stream())))
+
+    def ps_server_state(self, out) -> None:
+        """The processor-sharing servers' privileged state into out, a contiguous (B, S, 4)
+        float32 tensor on the handle's device (lbsim_ps_server_state): one kernel on the current
+        stream, valid after any reset or step."""
+        self.check(self.lib.lbsim_ps_server_state(self.h, ctypes.c_void_p(out.data_ptr()),
+                                                  ctypes.c_void_p(self._stream())))
+
     def server_pool_size(self) -> int:
         """Balancers per pool, 0 on a handle without pools (lbsim_server_pool_size)."""
         return int(self.lib.lbsim_server_pool_size(self.h))
@@ -656,6 +685,10 @@ class DeviceSnapshot:
         self.delay = delay
 
 
+_PS_CORES_OFF = ("{} on an env without processor-sharing servers: call "
+                 "lbsim_processor_sharing_enable first (service_discipline=\"ps\")")
+
+
 class VecLoadBalanceEnv:
     """num_envs independent LoadBalanceEnv instances stepped together on one GPU.
 
@@ -722,6 +755,11 @@ class VecLoadBalanceEnv:
     resets, cross traffic, server workers, action delay, pools or ground_truth() (LbsimError,
     code ENOTSUP; marllb_amd.ps.check_ps_config states the rule).  The default "fifo" runs the
     FIFO servers' kernels untouched.
+    ps_cores=array (with service_discipline="ps" only: LbsimError, code ENOTSUP, otherwise) gives
+    each processor-sharing server its own number of cores, (S,) or (B, S) integers in [1, 64]
+    (DESIGN.md §3.23): with n flows on c cores every flow runs at rate min(1, c / n) of
+    server_rate, the rate of ONE core.  set_ps_cores / get_ps_cores / clear_ps_cores change and
+    read them at any time; ps_state() is such an env's privileged view of its servers.
     """
 
     def __init__(self, num_envs: int, num_servers: int = 4, *, device=None,
@@ -731,10 +769,12 @@ class VecLoadBalanceEnv:
                  flow_stats: bool = False, server_availability: bool = False,
                  cross_traffic: bool = False, server_workers=False, action_delay=False,
                  max_delay_steps: int = 1, balancers_per_pool: int = 0,
-                 service_discipline: str = "fifo", **kwargs):
+                 service_discipline: str = "fifo", ps_cores=None, **kwargs):
         torch = _torch()
         if service_discipline not in ("fifo", "ps"):
             raise ValueError(f"Unknown service_discipline: {service_discipline}")
+        if ps_cores is not None and service_discipline != "ps":  # before any device is touched
+            raise _lib.LbsimError(_lib.ENOTSUP, _PS_CORES_OFF.format("ps_cores"))
         self.service_discipline = service_discipline
         if autoreset_mode not in ("same_step", "next_step"):
             raise ValueError(f"Unknown autoreset_mode: {autoreset_mode}")
@@ -771,7 +811,8 @@ class VecLoadBalanceEnv:
                             cross_traffic=cross_traffic,
                             server_workers=server_workers is not False and server_workers is not None,
                             action_delay=action_delay is not False and action_delay is not None,
-                            balancers_per_pool=self.balancers_per_pool)
+                            balancers_per_pool=self.balancers_per_pool,
+                            ps_cores=ps_cores is not None)
         self.device_index = _device_index(device)
         self.device = torch.device("cuda", self.device_index)
         self.trace = kwargs.get("trace")
@@ -786,6 +827,8 @@ class VecLoadBalanceEnv:
             self.handle.enable_server_pool(self.balancers_per_pool)
         if service_discipline == "ps":
             self.handle.enable_processor_sharing()
+            if ps_cores is not None:
+                self.set_ps_cores(ps_cores)
         if flow_stats:
             self.handle.enable_flow_stats()
         self.server_availability = bool(server_availability)
@@ -1160,6 +1203,71 @@ class VecLoadBalanceEnv:
     def clear_server_workers(self) -> None:
         """Every server back to one worker."""
         self.handle.clear_server_workers()
+
+    # ---- cores of processor-sharing servers (service_discipline="ps"; DESIGN.md §3.23)
+    def _ps_only(self, what: str) -> None:
+        if self.service_discipline != "ps":
+            raise _lib.LbsimError(_lib.ENOTSUP, _PS_CORES_OFF.format(what))
+
+    def set_ps_cores(self, cores) -> None:
+        """Per-server core counts of processor-sharing servers: cores (S,) or (B, S) integers in
+        [1, 64], a tensor or array on any device.  The n flows on server s of env b then run at
+        rate min(1, cores[b, s] / n) each, of server_rate, the rate of ONE core (capacity c *
+        server_rate: marllb_amd.randomize.sample_server_workers(B, S, choices,
+        keep_capacity=True) returns (counts, server_rate) for vec.set_ps_cores(counts);
+        vec.set_rates(None, server_rate)).  From the next launch on (step, reset, warm-up); queued
+        flows keep their remaining service.  A count out of range, or a non-integer one:
+        ValueError, the previous counts stay in force.  Not part of get_state(); a shard passes
+        its own rows.  graph_mode: the first call comes before the capture; later calls rewrite
+        the same device array, so replays see them."""
+        self._ps_only("set_ps_cores")
+        torch = _torch()
+        B, S = self.num_envs, self.num_servers
+        c = torch.as_tensor(cores)
+        if tuple(c.shape) not in ((S,), (B, S)):
+            raise ValueError(f"cores: expected shape ({S},) or ({B}, {S}), got {tuple(c.shape)}")
+        if c.is_floating_point():
+            if not bool((c == c.round()).all()):  # (NaN included)
+                raise ValueError("cores: expected integers")
+        elif c.dtype == torch.bool:
+            raise ValueError("cores: expected integers")
+        # out-of-range counts stay out of range as int32 (the device call rejects them)
+        c = c.to(torch.float64).clamp(-1.0, 65.0).to(device=self.device, dtype=torch.int32)
+        rows = B if c.dim() == 2 else 1
+        self.handle.set_ps_cores(c.reshape(rows, S).contiguous(), rows=rows)
+
+    def get_ps_cores(self):
+        """(B, S) int32 device tensor: the core counts in force (all 1 until set_ps_cores)."""
+        self._ps_only("get_ps_cores")
+        return self.handle.ps_cores()
+
+    def clear_ps_cores(self) -> None:
+        """Every server back to one core."""
+        self._ps_only("clear_ps_cores")
+        self.handle.clear_ps_cores()
+
+    def ps_state(self, out=None):
+        """(B, S, 4) f32 device tensor, columns PS_STATE_COLUMNS: the privileged view of the
+        processor-sharing servers as they stand after the last reset() or step() -- n (the flows
+        on the server), busy_cores (min(n, cores)), work_s (the unfinished work in seconds of one
+        core) and drain_s (seconds until the server is empty with no further arrival; equal to
+        work_s on a one-core server).  For a centralised critic; never normalised.  One small
+        kernel on the current stream, no allocation inside the library and no synchronisation.
+        out: a contiguous (B, S, 4) float32 tensor on the env's device to write into; by default a
+        new tensor, or (graph_mode) the same buffer every call."""
+        self._ps_only("ps_state")
+        torch = _torch()
+        shape = (self.num_envs, self.num_servers, len(PS_STATE_COLUMNS))
+        if out is None:
+            out = self._buf("ps_state", shape, torch.float32)
+        elif (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError(f"out: expected a contiguous float32 tensor of shape {shape} on "
+                             f"{self.device}")
+        if not self._reset_done:
+            raise RuntimeError("ps_state() before reset()")
+        self.handle.ps_server_state(out)
+        return out
 
     # ---- action latency (action_delay=True; DESIGN.md §3.19)
     def set_action_delay(self, seconds) -> None:
@@ -2044,6 +2152,32 @@ class LoadBalanceEnv:
 
     def clear_server_workers(self) -> None:
         self._workers_vec().clear_server_workers()
+
+    # ---- cores of processor-sharing servers (LoadBalanceEnv(service_discipline="ps",
+    #      ps_cores=[...]))
+    def _ps_vec(self) -> "VecLoadBalanceEnv":
+        if self._vec is None:
+            raise RuntimeError("ps cores need the GPU simulator (not reference_plumbing)")
+        return self._vec
+
+    def set_ps_cores(self, cores) -> None:
+        """The servers' core counts, (num_servers,) integers in [1, 64]
+        (VecLoadBalanceEnv.set_ps_cores of the one env)."""
+        c = np.asarray(cores)
+        if c.shape != (self.num_servers,):
+            raise ValueError(f"cores: expected ({self.num_servers},), got {c.shape}")
+        self._ps_vec().set_ps_cores(c)
+
+    def get_ps_cores(self) -> List[int]:
+        return self._ps_vec().get_ps_cores()[0].cpu().tolist()
+
+    def clear_ps_cores(self) -> None:
+        self._ps_vec().clear_ps_cores()
+
+    def ps_state(self) -> np.ndarray:
+        """(S, 4) float32, columns marllb_amd.PS_STATE_COLUMNS (VecLoadBalanceEnv.ps_state of the
+        one env)."""
+        return self._ps_vec().ps_state()[0].cpu().numpy()
 
     # ---- action latency (LoadBalanceEnv(action_delay=0.02 or True))
     def _delay_vec(self) -> "VecLoadBalanceEnv":

@@ -120,6 +120,21 @@ class MultiAgentLoadBalanceEnv:
     def clear_action_delay(self) -> None:
         self.env.clear_action_delay()
 
+    def set_ps_cores(self, cores) -> None:
+        """The servers' core counts, (total_servers,) in agent order: LoadBalanceEnv.set_ps_cores
+        (an env made with service_discipline="ps")."""
+        self.env.set_ps_cores(cores)
+
+    def get_ps_cores(self) -> List[int]:
+        return self.env.get_ps_cores()
+
+    def clear_ps_cores(self) -> None:
+        self.env.clear_ps_cores()
+
+    def ps_state(self) -> np.ndarray:
+        """(total_servers, 4) float32: LoadBalanceEnv.ps_state."""
+        return self.env.ps_state()
+
     def render(self, mode: str = "human"):
         return self.env.render(mode)
 
@@ -271,6 +286,21 @@ class VecMultiAgentLoadBalanceEnv:
 
     def clear_server_workers(self) -> None:
         self.vec.clear_server_workers()
+
+    def set_ps_cores(self, cores) -> None:
+        """Per-server core counts of processor-sharing servers, (S,) or (B, S) in agent order:
+        VecLoadBalanceEnv.set_ps_cores (an env made with service_discipline="ps")."""
+        self.vec.set_ps_cores(cores)
+
+    def get_ps_cores(self):
+        return self.vec.get_ps_cores()
+
+    def clear_ps_cores(self) -> None:
+        self.vec.clear_ps_cores()
+
+    def ps_state(self, out=None):
+        """(B, S, 4) f32, columns marllb_amd.PS_STATE_COLUMNS: VecLoadBalanceEnv.ps_state."""
+        return self.vec.ps_state(out)
 
     def set_action_delay(self, seconds) -> None:
         """Per-env control delay in seconds, a scalar or (B,): VecLoadBalanceEnv.set_action_delay

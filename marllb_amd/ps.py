@@ -1,7 +1,8 @@
 """Processor-sharing servers: VecLoadBalanceEnv(..., service_discipline="ps").
 
 Every server has one worker that the flows queued on it share equally, as an application host
-with more worker processes than cores shares its CPU.  check_ps_config states, without a device,
+with more worker processes than cores shares its CPU; ps_cores=... gives a server several cores
+(§3.23).  check_ps_config states, without a device,
 what lbsim_processor_sharing_enable accepts.
 """
 from __future__ import annotations
@@ -10,9 +11,11 @@ from . import _lib
 
 
 def check_ps_config(cfg, *, server_availability=False, cross_traffic=False, server_workers=False,
-                    action_delay=False, balancers_per_pool=0) -> None:
+                    action_delay=False, balancers_per_pool=0, ps_cores=False) -> None:
     """lbsim_processor_sharing_enable's rule on a config, before any handle exists: LbsimError
-    (code ENOTSUP) naming the option the processor-sharing dynamics have no code for."""
+    (code ENOTSUP) naming the option the processor-sharing dynamics have no code for.  ps_cores
+    (per-server core counts) refuses nothing: they compose with everything a
+    processor-sharing handle accepts."""
     no = None
     if cfg.assign_policy == _lib.POLICIES.index("alias"):
         no = "assign_policy ALIAS"

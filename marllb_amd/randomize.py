@@ -270,7 +270,9 @@ SERVER_RANGE = (1.0, 1.0e7)  # flows/s, make_config's range for a server rate
 def sample_server_workers(num_envs: int, num_servers: int, choices=(1, 2, 4), seed: int = 0,
                           keep_capacity: bool = True, *, server_rates=None, device=None):
     """-> (workers (B, S) int32, server_rate (B, S) float32) for
-    VecLoadBalanceEnv.set_server_workers and set_rates(None, server_rate).
+    VecLoadBalanceEnv.set_server_workers and set_rates(None, server_rate); on an env with
+    service_discipline="ps" the same pair gives the servers' cores:
+    vec.set_ps_cores(workers); vec.set_rates(None, server_rate).
 
     workers: each server's count, uniform over `choices` (integers in [1, 64]).
     server_rate: the rate of ONE worker.  server_rates (a scalar, (S,) or (B, S), flows/s; default
