@@ -125,7 +125,8 @@ enum lbsim_dyn_kernel {
   LBSIM_DYN_KERNEL_GROUP = 1,     /* dynamics_group_kernel: one lane per server, G-lane groups */
   LBSIM_DYN_KERNEL_WAVE = 2,      /* dynamics_wave_kernel: one wave per env                    */
   LBSIM_DYN_KERNEL_POOL = 3,      /* dynamics_pool_kernel: one G-lane group per server pool    */
-  LBSIM_DYN_KERNEL_PS = 4         /* dynamics_ps_kernel: processor-sharing servers, G-lane groups */
+  LBSIM_DYN_KERNEL_PS = 4,        /* dynamics_ps_kernel: processor-sharing servers, G-lane groups */
+  LBSIM_DYN_KERNEL_POOL_PS = 5    /* dynamics_pool_ps_kernel: a pool's servers processor-sharing   */
 };
 
 /* How lbsim_step runs; every choice produces the same bits.  FUSED: one launch per step whose
@@ -921,6 +922,48 @@ int lbsim_get_ps_cores(lbsim_t* h, int32_t* cores_out, void* stream);
 int lbsim_clear_ps_cores(lbsim_t* h, void* stream);
 size_t lbsim_ps_server_state_cols(void);
 int lbsim_ps_server_state(lbsim_t* h, float* state_out, void* stream);
+
+/* Shared server pools of processor-sharing servers: the discipline of a
+ * pool's servers is a property of the pool.  lbsim_server_pool_enable_ps is
+ * lbsim_server_pool_enable -- the same checks, allocations, messages and state sections -- and
+ * marks the pool's S physical servers processor-sharing ones of c cores each (section 3.23's rule;
+ * c = 1 until lbsim_set_pool_ps_cores).  Per (pool, server): the clock words V, acc, t_last and n
+ * entries {tag, ta, owner} in non-decreasing tag order, a new entry after every equal tag.  The
+ * pool's next arrival, the assignment by the member's own weight row and own counts, eligibility
+ * by the physical n < queue_capacity and the drop rule are section 3.21's; on the chosen server
+ * the completions due by ta go first, then advance(s, ta), tag = V + svc and the sorted insert,
+ * moved entries carrying their owner.  A completion pops the head: its sample tc - ta goes into
+ * the owner's reservoir (gid_owner, s), always drawn from the owner's reservoir stream at the
+ * owner's count, stamped with the pool's clock.  No new state section: the entries {tag - V, ta}
+ * are the first member's ring rows in tag order from the physical head, the owners pool_owner, the
+ * physical head | n << 16 pool_hc, acc the last_tc word of every member's row of that server, and
+ * a member's hc word the physical head, its own big flag and its own count.  balancers = 1 equals
+ * a lbsim_processor_sharing_enable handle with the same cores bit for bit.
+ * Calling lbsim_server_pool_enable_ps or lbsim_server_pool_enable on a handle whose pools were
+ * enabled the other way returns LBSIM_EINVAL.  Such a handle is a pool handle, not a
+ * lbsim_processor_sharing_enable one: lbsim_processor_sharing stays 0, lbsim_set_ps_cores and
+ * lbsim_ps_server_state keep refusing, every refusal of a pool handle holds, and
+ * lbsim_ground_truth returns LBSIM_ENOTSUP (lbsim_pool_ps_state is its view).  The steps launch
+ * dynamics_pool_ps_kernel (lbsim_dynamics_kernel: LBSIM_DYN_KERNEL_POOL_PS) and the handle's
+ * ordinary observe; no allocation or synchronisation is added to lbsim_step or lbsim_reset.
+ * lbsim_server_pool_discipline: 1 on such a handle, 0 with FIFO pools or none.
+ * lbsim_set_pool_ps_cores / lbsim_get_pool_ps_cores / lbsim_clear_pool_ps_cores: as the
+ * lbsim_*_ps_cores calls, with one row per POOL: `cores` is int32 [rows, S], rows = 1 or C =
+ * num_envs / balancers; cores_out int32 [C, S].  On any other handle LBSIM_ENOTSUP.
+ * lbsim_pool_ps_state: state_out float32 [num_envs, S, LBSIM_POOL_PS_STATE_COLS] on the device,
+ * each member's row describing the physical server: column 0 its flows n, 1 n minus the member's
+ * own count (what the other balancers put there), 2 the busy cores min(n, c), 3 the unfinished
+ * work in seconds of one core, 4 the seconds to drain (columns 2 and 3 of lbsim_ps_server_state
+ * on the physical entries).  LBSIM_EINVAL before the first reset.  One kernel on `stream`, no
+ * allocation, no synchronisation. */
+#define LBSIM_POOL_PS_STATE_COLS 5
+int lbsim_server_pool_enable_ps(lbsim_t* h, int32_t balancers);
+int lbsim_server_pool_discipline(const lbsim_t* h);
+int lbsim_set_pool_ps_cores(lbsim_t* h, const int32_t* cores, int32_t rows, void* stream);
+int lbsim_get_pool_ps_cores(lbsim_t* h, int32_t* cores_out, void* stream);
+int lbsim_clear_pool_ps_cores(lbsim_t* h, void* stream);
+size_t lbsim_pool_ps_state_cols(void);
+int lbsim_pool_ps_state(lbsim_t* h, float* state_out, void* stream);
 
 /* Stateless: n Vose alias tables of S weights each (device pointers), the O(n) build of
  * problem-07's realtime VPP plugin (realtime-mode/problem-07-realtime-deployment/vpp-plugin/

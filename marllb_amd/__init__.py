@@ -4,8 +4,9 @@ The hot path of the MARLLB reference (problem-03 LoadBalanceEnv.step/reset + pro
 feature collector) as hand-written gfx950 HIP kernels behind a C ABI (include/lbsim.h,
 liblbsim.so), with the reference's Gym-style API on top.
 """
-from .env import (FEATURE_NAMES, GROUND_TRUTH_COLUMNS, PS_STATE_COLUMNS, DeviceSnapshot,
-                  LoadBalanceEnv, LoadBalanceEnvGym, VecLoadBalanceEnv, make_config)
+from .env import (FEATURE_NAMES, GROUND_TRUTH_COLUMNS, POOL_PS_STATE_COLUMNS, PS_STATE_COLUMNS,
+                  DeviceSnapshot, LoadBalanceEnv, LoadBalanceEnvGym, VecLoadBalanceEnv,
+                  make_config)
 from .multi_agent import MultiAgentLoadBalanceEnv, VecMultiAgentLoadBalanceEnv
 from .pools import VecServerPoolEnv
 from .randomize import (burst_schedule, diurnal_schedule, outage_schedule,
@@ -26,5 +27,5 @@ __all__ = ["FEATURE_NAMES", "LoadBalanceEnv", "LoadBalanceEnvGym", "VecLoadBalan
            "sample_table_ids", "sample_cluster_sizes", "outage_schedule",
            "rolling_restart_schedule", "sample_cross_traffic", "sample_server_workers",
            "sample_action_delay", "GROUND_TRUTH_COLUMNS", "PS_STATE_COLUMNS", "VecServerPoolEnv",
-           "sample_pool_arrival_rates"]
+           "sample_pool_arrival_rates", "POOL_PS_STATE_COLUMNS"]
 __version__ = "0.1.0"

@@ -213,6 +213,13 @@ _SIGNATURES = {
     "lbsim_clear_ps_cores": (ctypes.c_int, [_P, _P]),
     "lbsim_ps_server_state": (ctypes.c_int, [_P, _P, _P]),
     "lbsim_ps_server_state_cols": (ctypes.c_size_t, []),
+    "lbsim_server_pool_enable_ps": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "lbsim_server_pool_discipline": (ctypes.c_int, [_P]),
+    "lbsim_set_pool_ps_cores": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P]),
+    "lbsim_get_pool_ps_cores": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_clear_pool_ps_cores": (ctypes.c_int, [_P, _P]),
+    "lbsim_pool_ps_state": (ctypes.c_int, [_P, _P, _P]),
+    "lbsim_pool_ps_state_cols": (ctypes.c_size_t, []),
     "lbsim_server_avail_enable": (ctypes.c_int, [_P]),
     "lbsim_set_server_avail": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_int32, _P]),

@@ -33,6 +33,8 @@ UNITS = [
     ("lbsim_dyn_pool.hip", ["-DLBSIM_DYN_MODE=1"], "dyn_pool_reset.o"),
     ("lbsim_dyn_ps.hip", ["-DLBSIM_DYN_MODE=0"], "dyn_ps_step.o"),
     ("lbsim_dyn_ps.hip", ["-DLBSIM_DYN_MODE=1"], "dyn_ps_reset.o"),
+    ("lbsim_dyn_pool_ps.hip", ["-DLBSIM_DYN_MODE=0"], "dyn_pool_ps_step.o"),
+    ("lbsim_dyn_pool_ps.hip", ["-DLBSIM_DYN_MODE=1"], "dyn_pool_ps_reset.o"),
     ("lbsim_obs.hip", [], "obs.o"),
     ("lbsim_pol.hip", [], "pol.o"),
     ("lbsim_step.hip", [], "step.o"),

@@ -136,6 +136,11 @@ struct lbsim {
   // lbsim_server_pool_enable: the physical FIFOs' words and owners (two state sections after all
   // the others, sections() below) and the widened reset mask, allocated once and never moved
   PoolArrays pool{};  // (A = 0: the handle has no pools)
+  // lbsim_server_pool_enable_ps (§3.24): the pools' servers are processor-sharing ones, and
+  // lbsim_set_pool_ps_cores' block, as ps_cores_buf below with one row per pool: the live c[C*S]
+  // dynamics_pool_ps_kernel reads, its staging copy and the offender count (nullptr: never set)
+  bool pool_ps = false;
+  int32_t* pool_ps_cores_buf = nullptr;
   bool ps = false;  // lbsim_processor_sharing_enable: processor-sharing servers
   // lbsim_set_ps_cores (§3.23): one block of 32-bit words, allocated by the first call and never
   // moved -- the live c[B*S] the PS dynamics kernel reads, its staging copy and the offender count
@@ -1251,6 +1256,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.action_delay = h->delay_buf != nullptr;
   in.pool = h->pool.A;
   in.ps = h->ps;
+  in.pool_ps = h->pool_ps;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -1258,6 +1264,14 @@ StepPlan plan_of(const lbsim_t* h) {
 int launch_dynamics(lbsim_t* h, const void* action, int dtype, int32_t* assign,
                     const uint8_t* mask, int mode, hipStream_t stream) {
   ProfScope ps(h, stream, mode == kModeStep ? 0 : 2);
+  if (h->pool_ps) {  // pools of processor-sharing servers: their own kernel (§3.24)
+    if (mode == kModeStep)
+      launch_dynamics_pool_ps_step(ctx(h), h->pool, action, dtype, assign, h->pool_ps_cores_buf,
+                                   stream);
+    else
+      launch_dynamics_pool_ps_reset(ctx(h), h->pool, mask, h->pool_ps_cores_buf, stream);
+    return launch_check(h, "dynamics_pool_ps_kernel");
+  }
   if (h->pool.A > 0) {  // shared server pools: their own kernel (mask: the widened one)
     if (mode == kModeStep) launch_dynamics_pool_step(ctx(h), h->pool, action, dtype, assign, stream);
     else launch_dynamics_pool_reset(ctx(h), h->pool, mask, stream);
@@ -1445,6 +1459,7 @@ int lbsim_destroy(lbsim_t* h) {
     if (h->cross_buf) (void)hipFree(h->cross_buf);
     if (h->workers_buf) (void)hipFree(h->workers_buf);
     if (h->ps_cores_buf) (void)hipFree(h->ps_cores_buf);
+    if (h->pool_ps_cores_buf) (void)hipFree(h->pool_ps_cores_buf);
     if (h->delay_buf) (void)hipFree(h->delay_buf);
     if (h->avail_buf) (void)hipFree(h->avail_buf);
     if (h->wtab_buf) (void)hipFree(h->wtab_buf);
@@ -2335,6 +2350,11 @@ int lbsim_ground_truth(lbsim_t* h, float* truth_out, void* stream) {
     return fail(h, LBSIM_ENOTSUP, "lbsim_ground_truth on a handle with processor-sharing servers "
                                   "(lbsim_processor_sharing_enable): its wait and backlog columns "
                                   "are FIFO quantities");
+  if (h->pool_ps)
+    return fail(h, LBSIM_ENOTSUP, "lbsim_ground_truth on a handle with pools of processor-sharing "
+                                  "servers (lbsim_server_pool_enable_ps): its wait and backlog "
+                                  "columns are FIFO quantities; lbsim_pool_ps_state is these "
+                                  "servers' view");
   DeviceGuard g(h->device);
   if (h->pool.A > 0) {  // shared server pools: the physical servers' rows
     launch_pool_truth(ctx(h), h->pool, h->cfg.server_rate, truth_out, (hipStream_t)stream);
@@ -2376,7 +2396,24 @@ int lbsim_clear_server_workers(lbsim_t* h, void* stream) {
 
 // ---- shared server pools (the rule: lbsim_pool.h, the kernels: lbsim_dyn_pool.hip)
 
+namespace {
+// lbsim_server_pool_enable (ps false) and lbsim_server_pool_enable_ps (§3.24): one rule, the
+// discipline of the pool's servers a property of the pool.
+int server_pool_enable(lbsim_t* h, int32_t balancers, bool ps);
+}  // namespace
+
 int lbsim_server_pool_enable(lbsim_t* h, int32_t balancers) {
+  return server_pool_enable(h, balancers, false);
+}
+int lbsim_server_pool_enable_ps(lbsim_t* h, int32_t balancers) {
+  return server_pool_enable(h, balancers, true);
+}
+int lbsim_server_pool_discipline(const lbsim_t* h) {
+  return h != nullptr && h->pool_ps ? 1 : 0;
+}
+
+namespace {
+int server_pool_enable(lbsim_t* h, int32_t balancers, bool ps) {
   if (h == nullptr) return LBSIM_EINVAL;
   switch (pool_enable_check(h->B, h->cfg.env_id_offset, balancers)) {
     case 1:
@@ -2392,6 +2429,9 @@ int lbsim_server_pool_enable(lbsim_t* h, int32_t balancers) {
     default: break;
   }
   if (h->pool.A > 0) {
+    if (ps != h->pool_ps)
+      return fail(h, LBSIM_EINVAL, "server pools are already on with %s servers",
+                  h->pool_ps ? "processor-sharing" : "FIFO");
     if (balancers == h->pool.A) return LBSIM_OK;
     return fail(h, LBSIM_EINVAL, "server pools are already on with balancers = %d", (int)h->pool.A);
   }
@@ -2441,9 +2481,11 @@ int lbsim_server_pool_enable(lbsim_t* h, int32_t balancers) {
   h->pool.owner = (uint8_t*)ptr[1];
   h->pool.mask = (uint8_t*)ptr[2];
   h->pool.A = balancers;
+  h->pool_ps = ps;
   h->plan = plan_of(h);  // the pool dynamics and the two-launch observe (make_plan)
   return LBSIM_OK;
 }
+}  // namespace
 
 int lbsim_server_pool_size(const lbsim_t* h) { return h == nullptr ? 0 : (int)h->pool.A; }
 
@@ -2488,53 +2530,52 @@ namespace {
 const char kPsCoresOff[] = "%s on a handle without processor-sharing servers: call "
                            "lbsim_processor_sharing_enable first";
 static_assert(kMaxWorkers == 64, "a PS server has 1 to 64 cores, a FIFO one 1 to 64 workers");
-unsigned ps_cores_blocks(const lbsim_t* h) {
-  return (unsigned)(((size_t)h->B * h->S + 255) / 256);
-}
-}  // namespace
 
-int lbsim_set_ps_cores(lbsim_t* h, const int32_t* cores, int32_t rows, void* stream) {
-  if (h == nullptr) return LBSIM_EINVAL;
-  if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_set_ps_cores");
-  if (cores == nullptr) return fail(h, LBSIM_EINVAL, "ps cores: cores is NULL");
-  if (rows != 1 && rows != h->B)
-    return fail(h, LBSIM_ESHAPE, "ps cores: rows must be 1 or num_envs = %d (got %d)", h->B, rows);
+// The three cores calls over one block of N = units * S counts: `buf` is the handle's
+// ps_cores_buf (units = num_envs, what = "ps cores") or pool_ps_cores_buf (units = the pools,
+// what = "pool ps cores", §3.24); unit_name names the row count a caller may pass.
+int cores_set(lbsim_t* h, int32_t*& buf, int units, const char* what, const char* unit_name,
+              const int32_t* cores, int32_t rows, void* stream) {
+  if (cores == nullptr) return fail(h, LBSIM_EINVAL, "%s: cores is NULL", what);
+  if (rows != 1 && rows != units)
+    return fail(h, LBSIM_ESHAPE, "%s: rows must be 1 or %s = %d (got %d)", what, unit_name, units,
+                rows);
   DeviceGuard g(h->device);
   const hipStream_t s = (hipStream_t)stream;
-  const size_t BS = (size_t)h->B * h->S, words = 2 * BS + 1;
-  const bool first = h->ps_cores_buf == nullptr;
-  int32_t* live = h->ps_cores_buf;
+  const size_t N = (size_t)units * h->S, words = 2 * N + 1;
+  const bool first = buf == nullptr;
+  int32_t* live = buf;
   if (first) {  // (the first call: before a graph capture, as §3.10's rate arrays)
     void* p = nullptr;
     if (hipMalloc(&p, words * 4) != hipSuccess)
       return fail(h, LBSIM_ENOMEM, "hipMalloc(%zu) failed", words * 4);
     live = (int32_t*)p;
   }
-  int32_t* const stg = live + BS;
-  uint32_t* const bad = (uint32_t*)(live + 2 * BS);
+  int32_t* const stg = live + N;
+  uint32_t* const bad = (uint32_t*)(live + 2 * N);
   int rc = LBSIM_OK;
   uint32_t nbad = 0;
   if (hipMemsetAsync(bad, 0, sizeof(uint32_t), s) != hipSuccess) {
-    rc = fail(h, LBSIM_EDEVICE, "ps cores: hipMemsetAsync failed");
+    rc = fail(h, LBSIM_EDEVICE, "%s: hipMemsetAsync failed", what);
   } else {
-    hipLaunchKernelGGL(workers_convert_kernel, dim3(ps_cores_blocks(h)), dim3(256), 0, s, cores,
-                       (int)rows, (int64_t)BS, h->S, stg, bad);
+    hipLaunchKernelGGL(workers_convert_kernel, dim3(blocks256(N)), dim3(256), 0, s, cores,
+                       (int)rows, (int64_t)N, h->S, stg, bad);
     rc = launch_check(h, "workers_convert_kernel");
     if (rc == LBSIM_OK &&
         (hipMemcpyAsync(&nbad, bad, sizeof(nbad), hipMemcpyDeviceToHost, s) != hipSuccess ||
          hipStreamSynchronize(s) != hipSuccess))
-      rc = fail(h, LBSIM_EDEVICE, "ps cores: conversion failed");
+      rc = fail(h, LBSIM_EDEVICE, "%s: conversion failed", what);
   }
   if (rc == LBSIM_OK && nbad != 0u)  // what was in force stays (before the first call: one each)
-    rc = fail(h, LBSIM_EINVAL, "ps cores: %u count(s) outside [1, %d]", nbad, (int)kMaxWorkers);
+    rc = fail(h, LBSIM_EINVAL, "%s: %u count(s) outside [1, %d]", what, nbad, (int)kMaxWorkers);
   if (rc == LBSIM_OK &&
-      hipMemcpyAsync(live, stg, BS * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-    rc = fail(h, LBSIM_EDEVICE, "ps cores: device copy failed");
+      hipMemcpyAsync(live, stg, N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    rc = fail(h, LBSIM_EDEVICE, "%s: device copy failed", what);
   if (first) {
     // the block is the handle's only once it holds valid counts (the copy is ordered on s before
     // every later launch of the caller's on it, as a set call's always is)
     if (rc == LBSIM_OK) {
-      h->ps_cores_buf = live;
+      buf = live;
     } else {
       (void)hipStreamSynchronize(s);
       (void)hipFree(live);
@@ -2543,34 +2584,92 @@ int lbsim_set_ps_cores(lbsim_t* h, const int32_t* cores, int32_t rows, void* str
   return rc;
 }
 
-int lbsim_get_ps_cores(lbsim_t* h, int32_t* cores_out, void* stream) {
-  if (h == nullptr) return LBSIM_EINVAL;
-  if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_get_ps_cores");
-  if (cores_out == nullptr) return fail(h, LBSIM_EINVAL, "ps cores: cores_out is NULL");
+int cores_get(lbsim_t* h, const int32_t* buf, int units, const char* what, int32_t* cores_out,
+              void* stream) {
+  if (cores_out == nullptr) return fail(h, LBSIM_EINVAL, "%s: cores_out is NULL", what);
   DeviceGuard g(h->device);
-  const size_t BS = (size_t)h->B * h->S;
-  if (h->ps_cores_buf == nullptr) {  // never set: every count 1 (no offender: bad is not touched)
-    hipLaunchKernelGGL(workers_convert_kernel, dim3(ps_cores_blocks(h)), dim3(256), 0,
-                       (hipStream_t)stream, (const int32_t*)nullptr, 1, (int64_t)BS, h->S,
+  const size_t N = (size_t)units * h->S;
+  if (buf == nullptr) {  // never set: every count 1 (no offender: bad is not touched)
+    hipLaunchKernelGGL(workers_convert_kernel, dim3(blocks256(N)), dim3(256), 0,
+                       (hipStream_t)stream, (const int32_t*)nullptr, 1, (int64_t)N, h->S,
                        cores_out, (uint32_t*)nullptr);
     return launch_check(h, "workers_convert_kernel");
   }
-  if (hipMemcpyAsync(cores_out, h->ps_cores_buf, BS * 4, hipMemcpyDeviceToDevice,
-                     (hipStream_t)stream) != hipSuccess)
-    return fail(h, LBSIM_EDEVICE, "ps cores: device copy failed");
+  if (hipMemcpyAsync(cores_out, buf, N * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) !=
+      hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "%s: device copy failed", what);
   return LBSIM_OK;
+}
+
+int cores_clear(lbsim_t* h, int32_t* buf, int units, void* stream) {
+  if (buf == nullptr) return LBSIM_OK;  // never set: one core each already
+  DeviceGuard g(h->device);
+  const size_t N = (size_t)units * h->S;
+  hipLaunchKernelGGL(workers_convert_kernel, dim3(blocks256(N)), dim3(256), 0,
+                     (hipStream_t)stream, (const int32_t*)nullptr, 1, (int64_t)N, h->S, buf,
+                     (uint32_t*)(buf + 2 * N));
+  return launch_check(h, "workers_convert_kernel");
+}
+}  // namespace
+
+int lbsim_set_ps_cores(lbsim_t* h, const int32_t* cores, int32_t rows, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_set_ps_cores");
+  return cores_set(h, h->ps_cores_buf, h->B, "ps cores", "num_envs", cores, rows, stream);
+}
+
+int lbsim_get_ps_cores(lbsim_t* h, int32_t* cores_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_get_ps_cores");
+  return cores_get(h, h->ps_cores_buf, h->B, "ps cores", cores_out, stream);
 }
 
 int lbsim_clear_ps_cores(lbsim_t* h, void* stream) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (!h->ps) return fail(h, LBSIM_ENOTSUP, kPsCoresOff, "lbsim_clear_ps_cores");
-  if (h->ps_cores_buf == nullptr) return LBSIM_OK;  // never set: one core each already
+  return cores_clear(h, h->ps_cores_buf, h->B, stream);
+}
+
+// ---- pools of processor-sharing servers (the kernels: lbsim_dyn_pool_ps.hip):
+//      the physical servers' cores, one row per pool, and their privileged view
+namespace {
+const char kPoolPsOff[] = "%s on a handle without pools of processor-sharing servers: call "
+                          "lbsim_server_pool_enable_ps first";
+int pool_count(const lbsim_t* h) { return h->B / (int)h->pool.A; }
+}  // namespace
+
+int lbsim_set_pool_ps_cores(lbsim_t* h, const int32_t* cores, int32_t rows, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->pool_ps) return fail(h, LBSIM_ENOTSUP, kPoolPsOff, "lbsim_set_pool_ps_cores");
+  return cores_set(h, h->pool_ps_cores_buf, pool_count(h), "pool ps cores", "the pools", cores,
+                   rows, stream);
+}
+
+int lbsim_get_pool_ps_cores(lbsim_t* h, int32_t* cores_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->pool_ps) return fail(h, LBSIM_ENOTSUP, kPoolPsOff, "lbsim_get_pool_ps_cores");
+  return cores_get(h, h->pool_ps_cores_buf, pool_count(h), "pool ps cores", cores_out, stream);
+}
+
+int lbsim_clear_pool_ps_cores(lbsim_t* h, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->pool_ps) return fail(h, LBSIM_ENOTSUP, kPoolPsOff, "lbsim_clear_pool_ps_cores");
+  return cores_clear(h, h->pool_ps_cores_buf, pool_count(h), stream);
+}
+
+size_t lbsim_pool_ps_state_cols(void) { return (size_t)LBSIM_POOL_PS_STATE_COLS; }
+
+int lbsim_pool_ps_state(lbsim_t* h, float* state_out, void* stream) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!h->pool_ps) return fail(h, LBSIM_ENOTSUP, kPoolPsOff, "lbsim_pool_ps_state");
+  if (state_out == nullptr) return fail(h, LBSIM_EINVAL, "pool ps state: state_out is NULL");
+  if (((uintptr_t)state_out & 3u) != 0u)
+    return fail(h, LBSIM_EINVAL, "pool ps state: state_out must be aligned to 4 bytes");
+  if (!h->initialised)
+    return fail(h, LBSIM_EINVAL, "call lbsim_reset before lbsim_pool_ps_state");
   DeviceGuard g(h->device);
-  const size_t BS = (size_t)h->B * h->S;
-  hipLaunchKernelGGL(workers_convert_kernel, dim3(ps_cores_blocks(h)), dim3(256), 0,
-                     (hipStream_t)stream, (const int32_t*)nullptr, 1, (int64_t)BS, h->S,
-                     h->ps_cores_buf, (uint32_t*)(h->ps_cores_buf + 2 * BS));
-  return launch_check(h, "workers_convert_kernel");
+  launch_pool_ps_state(ctx(h), h->pool, h->pool_ps_cores_buf, state_out, (hipStream_t)stream);
+  return launch_check(h, "pool_ps_state_kernel");
 }
 
 size_t lbsim_ps_server_state_cols(void) { return (size_t)LBSIM_PS_STATE_COLS; }
@@ -2590,7 +2689,8 @@ int lbsim_ps_server_state(lbsim_t* h, float* state_out, void* stream) {
   a.acc = h->st.last_tc;
   a.cores = h->ps_cores_buf;
   a.B = h->B, a.S = h->S, a.Q = h->Q;
-  hipLaunchKernelGGL(ps_state_kernel, dim3(ps_cores_blocks(h)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(ps_state_kernel, dim3(blocks256((size_t)h->B * h->S)), dim3(256), 0,
+                     (hipStream_t)stream,
                      a, state_out);
   return launch_check(h, "ps_state_kernel");
 }

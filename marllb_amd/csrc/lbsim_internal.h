@@ -14,6 +14,8 @@
 //   lbsim_ps.h         processor-sharing servers: the host / device rule of a server's virtual clock
 //   lbsim_dyn_ps.hip   dynamics_ps_kernel launchers (processor sharing); built twice
 //                      (-DLBSIM_DYN_MODE=0 step, 1 reset)
+//   lbsim_dyn_pool_ps.hip  dynamics_pool_ps_kernel launchers (pools of processor-sharing servers);
+//                      built twice (-DLBSIM_DYN_MODE=0 step, 1 reset, with lbsim_pool_ps_state's kernel)
 //   lbsim_dyn.hip      dynamics_kernel / dynamics_group_kernel launchers; built three times
 //                      (-DLBSIM_DYN_MODE=0: step, 1: reset, 2: the next-step auto-reset step)
 //   lbsim_obs.hip      observe_kernel launchers
@@ -117,6 +119,18 @@ void launch_dynamics_ps_step(const LaunchCtx& L, const void* action, int dtype, 
                              const int32_t* cores, hipStream_t s);
 void launch_dynamics_ps_reset(const LaunchCtx& L, const uint8_t* mask, const int32_t* cores,
                               hipStream_t s);
+
+// The dynamics of a handle whose shared server pools have processor-sharing servers
+// (lbsim_dyn_pool_ps.hip: dynamics_pool_ps_kernel, §3.24; the plan is a PS pool one, pa holds the
+// physical servers' words and owners; cores: the physical servers' core counts [C * S], or
+// nullptr: one each).  A reset's mask is the widened one.
+void launch_dynamics_pool_ps_step(const LaunchCtx& L, const PoolArrays& pa, const void* action,
+                                  int dtype, int32_t* assign, const int32_t* cores, hipStream_t s);
+void launch_dynamics_pool_ps_reset(const LaunchCtx& L, const PoolArrays& pa, const uint8_t* mask,
+                                   const int32_t* cores, hipStream_t s);
+// lbsim_pool_ps_state: out[B, S, 5], each member's row the physical server's.
+void launch_pool_ps_state(const LaunchCtx& L, const PoolArrays& pa, const int32_t* cores,
+                          float* out, hipStream_t s);
 
 void launch_observe_step(const LaunchCtx& L, const ObsOutputs& o, const uint8_t* mask,
                          hipStream_t s);

@@ -66,6 +66,7 @@ struct PlanInput {
   bool action_delay = false;  // action latency is on (lbsim_action_delay_enable)
   int pool = 0;  // balancers per shared server pool (lbsim_server_pool_enable); 0: no pools
   bool ps = false;  // processor-sharing servers (lbsim_processor_sharing_enable)
+  bool pool_ps = false;  // the pools' servers are processor-sharing ones (lbsim_server_pool_enable_ps)
 };
 
 enum StepForm { kStepWave, kStepGroupFused, kStepTwoLaunch };
@@ -81,7 +82,7 @@ constexpr int kObserveSplitS = 16;
 constexpr unsigned env_lane_block(int maxs) { return maxs <= 8 ? 256u : 128u; }
 
 struct DynPlan {
-  int kernel;   // lbsim_dyn_kernel: LBSIM_DYN_KERNEL_ENV_LANE | _GROUP | _WAVE | _POOL | _PS
+  int kernel;   // lbsim_dyn_kernel: LBSIM_DYN_KERNEL_ENV_LANE | _GROUP | _WAVE | _POOL | _PS | _POOL_PS
   int width;    // env-lane: MAXS 4 | 8 | 16; group: G lanes per env; wave: NG ring registers;
                 // pool: G lanes per pool; ps: G lanes per env
   bool full;    // group: dynamics_group_full_kernel (every feature's code, its own budget)
@@ -179,7 +180,10 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
     DynPlan d{};
     if (pool) {
       const int pg = pool_group_lanes(S, in.pool, fl);
-      d = {LBSIM_DYN_KERNEL_POOL, pg, false, 0, 64 / pg, blocks(B / in.pool, 64 / pg), 64u};
+      // (pools of processor-sharing servers, DESIGN.md §3.24: dynamics_pool_ps_kernel, the same
+      // groups and grid)
+      const int kernel = in.pool_ps ? LBSIM_DYN_KERNEL_POOL_PS : LBSIM_DYN_KERNEL_POOL;
+      d = {kernel, pg, false, 0, 64 / pg, blocks(B / in.pool, 64 / pg), 64u};
     } else if (ps) {
       int pg = 2;
       if (fl >= S && (fl == 4 || fl == 8 || fl == 16 || fl == 32 || fl == 64)) pg = fl;

@@ -16,10 +16,15 @@ MAX_SERVERS = 16    # kPoolMaxServers
 
 
 def check_pool_config(cfg, balancers: int, *, flow_stats=False, server_availability=False,
-                      cross_traffic=False, server_workers=False, action_delay=False) -> None:
+                      cross_traffic=False, server_workers=False, action_delay=False,
+                      pool_discipline="fifo") -> None:
     """lbsim_server_pool_enable's rule on a config, before any handle exists: ValueError for a
     pool size outside [1, 8] or one that does not divide num_envs and env_id_offset; LbsimError
-    (code ENOTSUP) naming the option the pool dynamics have no code for."""
+    (code ENOTSUP) naming the option the pool dynamics have no code for.  pool_discipline "ps"
+    (lbsim_server_pool_enable_ps) accepts exactly the same configs; any other
+    value than "fifo" or "ps" is a ValueError."""
+    if pool_discipline not in ("fifo", "ps"):
+        raise ValueError(f"Unknown pool_discipline: {pool_discipline}")
     A = int(balancers)
     if A < 1 or A > MAX_BALANCERS:
         raise ValueError(f"server pools: balancers must be in [1, {MAX_BALANCERS}] (got {A})")
@@ -71,6 +76,10 @@ class VecServerPoolEnv:
     true_state()   -> (C, S, 8): the physical servers (ground-truth columns; column 1 is 0)
     others_load()  -> (C, A, S): the flows the OTHER balancers have on each server
     Every other keyword goes to VecLoadBalanceEnv; .env is that env (set_rates, seed, ...).
+    pool_discipline="ps" (DESIGN.md §3.24): the physical servers are processor-sharing ones
+    (pool_ps_cores=..., set_pool_ps_cores / get_pool_ps_cores / clear_pool_ps_cores /
+    pool_ps_state forwarded); true_state() is then (C, S, 5), the leader's pool_ps_state() rows
+    with column 1 set to 0, and others_load() their column 1.
     """
 
     def __init__(self, num_pools: int, num_balancers: int, num_servers: int = 4, **kwargs):
@@ -125,16 +134,40 @@ class VecServerPoolEnv:
     def true_state(self):
         """(C, S, 8) f32: the pool leader's ground-truth rows -- the physical queue length, busy,
         cpu, wait_s, backlog_s, up, capacity -- with column 1 (n_hidden, a per-member number:
-        others_load) set to 0."""
-        gt = self.env.ground_truth()
+        others_load) set to 0.  On a pool of processor-sharing servers (pool_discipline="ps"):
+        (C, S, 5) f32, the leader's pool_ps_state() rows -- n, n_others, busy_cores, work_s,
+        drain_s (env.POOL_PS_STATE_COLUMNS) -- with column 1 (n_others) set to 0."""
+        gt = self._truth()
         t = gt.view(self.num_pools, self.num_balancers, self.num_servers, gt.shape[-1])[:, 0].clone()
         t[:, :, 1] = 0.0
         return t
 
+    def _truth(self):
+        # a PS pool's privileged rows are pool_ps_state()'s (C, S, 5): n, n_others, busy_cores,
+        # work_s, drain_s -- column 1 the per-member number there too
+        if self.env.pool_discipline == "ps":
+            return self.env.pool_ps_state()
+        return self.env.ground_truth()
+
+    # ---- pools of processor-sharing servers (pool_discipline="ps"): VecLoadBalanceEnv's
+    def set_pool_ps_cores(self, cores) -> None:
+        self.env.set_pool_ps_cores(cores)
+
+    def get_pool_ps_cores(self):
+        return self.env.get_pool_ps_cores()
+
+    def clear_pool_ps_cores(self) -> None:
+        self.env.clear_pool_ps_cores()
+
+    def pool_ps_state(self, out=None):
+        return self.env.pool_ps_state(out)
+
     def others_load(self):
         """(C, A, S) f32: the flows in flight on each server that OTHER balancers of the pool
-        forwarded -- exactly the error of each balancer's own queue estimate (column 0)."""
-        gt = self.env.ground_truth()
+        forwarded -- exactly the error of each balancer's own queue estimate (column 0).  Column 1
+        of ground_truth() (n_hidden), or of pool_ps_state() (n_others) on a pool of
+        processor-sharing servers."""
+        gt = self._truth()
         return gt.view(self.num_pools, self.num_balancers, self.num_servers, gt.shape[-1])[..., 1].clone()
 
     def close(self) -> None:
