@@ -126,7 +126,8 @@ enum lbsim_dyn_kernel {
   LBSIM_DYN_KERNEL_WAVE = 2,      /* dynamics_wave_kernel: one wave per env                    */
   LBSIM_DYN_KERNEL_POOL = 3,      /* dynamics_pool_kernel: one G-lane group per server pool    */
   LBSIM_DYN_KERNEL_PS = 4,        /* dynamics_ps_kernel: processor-sharing servers, G-lane groups */
-  LBSIM_DYN_KERNEL_POOL_PS = 5    /* dynamics_pool_ps_kernel: a pool's servers processor-sharing   */
+  LBSIM_DYN_KERNEL_POOL_PS = 5,   /* dynamics_pool_ps_kernel: a pool's servers processor-sharing   */
+  LBSIM_DYN_KERNEL_ACK = 6        /* dynamics_group_ack_kernel: duration samples at every data ACK */
 };
 
 /* How lbsim_step runs; every choice produces the same bits.  FUSED: one launch per step whose
@@ -886,6 +887,47 @@ int lbsim_server_pool_size(const lbsim_t* h);
  * lbsim_processor_sharing: 1 on an enabled handle, else 0. */
 int lbsim_processor_sharing_enable(lbsim_t* h);
 int lbsim_processor_sharing(const lbsim_t* h);
+
+/* Duration samples at every data ACK, opt-in per handle: the data plane
+ * records a flow_duration sample on every pure ACK after the handshake, so a flow offers its
+ * server's duration reservoir one sample per data ACK instead of one at its completion.  All
+ * quantities are integer us.  A flow on server s that arrived at ta starts service at t0 =
+ * max(ta, tc of its predecessor on s), completes at tc = t0 + svc and emits k = min(max_acks,
+ * max(1, svc / ack_us)) ACKs, ACK j = 1..k at t_j = t0 + (svc * j) / k (so t_k = tc); each offers
+ * the flow's age t_j - ta, stamped (clock * dt + t_j) / 1000 ms, to the duration reservoir of s,
+ * in the step whose (0, dt] holds t_j -- the warm-up steps of a reset included.  The duration
+ * reservoir has its own count and {us, ts} records (state sections res_dur, 1024 S bytes per env,
+ * and res_count_dur, 4 S bytes per env: lbsim_state_size grows, lbsim_set_state rejects a plain
+ * handle's snapshot by size) and draws every sample from the reservoir stream under the word
+ * (2 << 24) | (1 << 17) | s.  The fct reservoir, the queues, the counters and observation columns
+ * 0-5 are bit for bit those of a handle without the option; columns 6-10 are the features of the
+ * duration reservoir.
+ * lbsim_ack_samples_enable: max_acks in [1, 32] (LBSIM_EINVAL otherwise), before the handle's
+ * first lbsim_reset (LBSIM_EINVAL after it; a second call with the same value is a no-op, with
+ * another LBSIM_EINVAL).  LBSIM_ENOTSUP, the message naming the option, with lost_fin_prob > 0,
+ * fail_prob > 0, duration_mode SERVICE, reservoir_mode VPP, n_flow_on_mode VPP or
+ * next_step_reset, and on a handle with server availability, cross traffic, server workers,
+ * action delay, server pools, processor sharing, flow statistics, workload tables, a trace bank of
+ * several traces or a trace schedule; on an enabled handle those opt-ins return LBSIM_ENOTSUP.
+ * The five assignment policies, Poisson arrivals and a single trace, per-env rates, rate
+ * schedules, normalize_obs, masked resets, lbsim_get_state / lbsim_set_state, lbsim_state_save /
+ * lbsim_state_load, lbsim_ground_truth and hipGraph capture of lbsim_step work as on any handle.
+ * The steps and resets launch dynamics_group_ack_kernel (lbsim_dynamics_kernel:
+ * LBSIM_DYN_KERNEL_ACK) and the general observe; no allocation or synchronisation is added to
+ * lbsim_step or lbsim_reset.
+ * lbsim_ack_samples: max_acks of an enabled handle, else 0.
+ * lbsim_set_ack_interval: us[rows] host int32 in [1, 2^30], rows = 1 (every env) or num_envs; in
+ * force from the next launch on (a flow in service then places its remaining ACKs by the new
+ * interval).  A value out of range: LBSIM_EINVAL, the previous intervals stay in force.  The call
+ * copies synchronously into a device array that never moves, so a captured graph sees it.
+ * lbsim_get_ack_interval: us_out[num_envs] host int32.  lbsim_clear_ack_interval: every env back
+ * to 1000 us, the value after the enable.  All three return LBSIM_ENOTSUP on a handle without the
+ * option.  The intervals are not part of the state. */
+int lbsim_ack_samples_enable(lbsim_t* h, int32_t max_acks);
+int lbsim_ack_samples(const lbsim_t* h);
+int lbsim_set_ack_interval(lbsim_t* h, const int32_t* us, int rows);
+int lbsim_get_ack_interval(lbsim_t* h, int32_t* us_out);
+int lbsim_clear_ack_interval(lbsim_t* h);
 
 /* Cores of processor-sharing servers, on a handle with
  * lbsim_processor_sharing_enable (LBSIM_ENOTSUP on any other): server s of env b has c = cores[b, s]

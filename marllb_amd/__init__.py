@@ -10,7 +10,8 @@ from .env import (FEATURE_NAMES, GROUND_TRUTH_COLUMNS, POOL_PS_STATE_COLUMNS, PS
 from .multi_agent import MultiAgentLoadBalanceEnv, VecMultiAgentLoadBalanceEnv
 from .pools import VecServerPoolEnv
 from .randomize import (burst_schedule, diurnal_schedule, outage_schedule,
-                        rolling_restart_schedule, sample_action_delay, sample_cluster_sizes,
+                        rolling_restart_schedule, sample_ack_interval, sample_action_delay,
+                        sample_cluster_sizes,
                         sample_cross_traffic, sample_pool_arrival_rates, sample_rates,
                         sample_server_workers, schedule_phase)
 from .spaces import Box, MultiDiscrete
@@ -27,5 +28,5 @@ __all__ = ["FEATURE_NAMES", "LoadBalanceEnv", "LoadBalanceEnvGym", "VecLoadBalan
            "sample_table_ids", "sample_cluster_sizes", "outage_schedule",
            "rolling_restart_schedule", "sample_cross_traffic", "sample_server_workers",
            "sample_action_delay", "GROUND_TRUTH_COLUMNS", "PS_STATE_COLUMNS", "VecServerPoolEnv",
-           "sample_pool_arrival_rates", "POOL_PS_STATE_COLUMNS"]
+           "sample_pool_arrival_rates", "POOL_PS_STATE_COLUMNS", "sample_ack_interval"]
 __version__ = "0.1.0"

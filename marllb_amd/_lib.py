@@ -206,6 +206,11 @@ _SIGNATURES = {
     "lbsim_action_delay_load": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P, _P]),
     "lbsim_server_pool_enable": (ctypes.c_int, [_P, ctypes.c_int32]),
     "lbsim_server_pool_size": (ctypes.c_int, [_P]),
+    "lbsim_ack_samples_enable": (ctypes.c_int, [_P, ctypes.c_int32]),
+    "lbsim_ack_samples": (ctypes.c_int, [_P]),
+    "lbsim_set_ack_interval": (ctypes.c_int, [_P, _P, ctypes.c_int]),
+    "lbsim_get_ack_interval": (ctypes.c_int, [_P, _P]),
+    "lbsim_clear_ack_interval": (ctypes.c_int, [_P]),
     "lbsim_processor_sharing_enable": (ctypes.c_int, [_P]),
     "lbsim_processor_sharing": (ctypes.c_int, [_P]),
     "lbsim_set_ps_cores": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P]),

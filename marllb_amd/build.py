@@ -29,6 +29,8 @@ UNITS = [
     ("lbsim_dyn.hip", ["-DLBSIM_DYN_MODE=2"], "dyn_step_nr.o"),
     ("lbsim_dyn_delay.hip", ["-DLBSIM_DYN_MODE=0"], "dyn_delay_step.o"),
     ("lbsim_dyn_delay.hip", ["-DLBSIM_DYN_MODE=2"], "dyn_delay_step_nr.o"),
+    ("lbsim_dyn_ack.hip", ["-DLBSIM_DYN_MODE=0"], "dyn_ack_step.o"),
+    ("lbsim_dyn_ack.hip", ["-DLBSIM_DYN_MODE=1"], "dyn_ack_reset.o"),
     ("lbsim_dyn_pool.hip", ["-DLBSIM_DYN_MODE=0"], "dyn_pool_step.o"),
     ("lbsim_dyn_pool.hip", ["-DLBSIM_DYN_MODE=1"], "dyn_pool_reset.o"),
     ("lbsim_dyn_ps.hip", ["-DLBSIM_DYN_MODE=0"], "dyn_ps_step.o"),

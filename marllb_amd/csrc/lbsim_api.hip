@@ -146,6 +146,11 @@ struct lbsim {
   // moved -- the live c[B*S] the PS dynamics kernel reads, its staging copy and the offender count
   // (nullptr: never set, every server one core)
   int32_t* ps_cores_buf = nullptr;
+  // lbsim_ack_samples_enable: max_acks (0: off) and the envs' ACK intervals
+  // [B] in us on the device, allocated once and never moved; the enable also allocates the
+  // res_dur / res_count_dur state sections (sections() below)
+  int32_t ack_max = 0;
+  int32_t* ack_us = nullptr;
   bool initialised;  // a full reset has been issued
   bool reset_seen = false;  // any lbsim_reset (or lbsim_set_state) has been issued
   std::string err;
@@ -176,6 +181,10 @@ const char kPoolNoCompose[] = "%s on a handle with shared server pools "
 // An opt-in refused on a handle with processor-sharing servers (not composed).
 const char kPsNoCompose[] = "%s on a handle with processor-sharing servers "
                             "(lbsim_processor_sharing_enable): not supported together";
+
+// An opt-in refused on a handle with duration samples at every data ACK.
+const char kAckNoCompose[] = "%s on a handle with ack samples (lbsim_ack_samples_enable): not "
+                             "supported together";
 
 // Scoped hipSetDevice that restores the caller's current device (torch keeps its own).
 struct DeviceGuard {
@@ -357,7 +366,11 @@ std::vector<Section> sections(lbsim_t* h) {
   if (h->prm.leak || h->cross_buf != nullptr) v.push_back({(void**)&s.lost_on, BS * 4});
   // the duration plane: only when a flow's duration sample can differ from its fct; split
   // handles (lost-FIN): {us, ts} records, the duration count, the pending guesses, lf_over
-  if (dur_plane(h->prm)) v.push_back({(void**)&s.res_dur, BSK * (h->prm.split ? 8 : 4)});
+  // (an ACK-samples handle, §3.25: {us, ts} records and the duration count, nothing pending)
+  const bool ack = h->ack_max > 0;
+  if (dur_plane(h->prm) || ack)
+    v.push_back({(void**)&s.res_dur, BSK * (h->prm.split || ack ? 8 : 4)});
+  if (ack) v.push_back({(void**)&s.res_count_dur, BS * 4});
   if (h->prm.split) {
     v.push_back({(void**)&s.res_count_dur, BS * 4});
     v.push_back({(void**)&s.pend_hc, BS * 4});
@@ -1257,6 +1270,7 @@ StepPlan plan_of(const lbsim_t* h) {
   in.pool = h->pool.A;
   in.ps = h->ps;
   in.pool_ps = h->pool_ps;
+  in.ack_samples = h->ack_max > 0;
   in.dyn_mapping = h->cfg.dyn_mapping, in.step_kernel = h->cfg.step_kernel, in.simds = h->simds;
   return make_plan(in, ov);
 }
@@ -1276,6 +1290,12 @@ int launch_dynamics(lbsim_t* h, const void* action, int dtype, int32_t* assign,
     if (mode == kModeStep) launch_dynamics_pool_step(ctx(h), h->pool, action, dtype, assign, stream);
     else launch_dynamics_pool_reset(ctx(h), h->pool, mask, stream);
     return launch_check(h, "dynamics_pool_kernel");
+  }
+  if (h->ack_max > 0) {  // ACK samples: the full form with the ACK code, step and reset (§3.25)
+    const AckSamples as{h->ack_us, h->ack_max};
+    if (mode == kModeStep) launch_dynamics_ack_step(ctx(h), as, action, dtype, assign, stream);
+    else launch_dynamics_ack_reset(ctx(h), as, mask, stream);
+    return launch_check(h, "dynamics_group_ack_kernel");
   }
   if (h->ps) {  // processor-sharing servers: their own kernel
     if (mode == kModeStep)
@@ -1676,6 +1696,8 @@ int lbsim_set_trace_bank(lbsim_t* h, const uint32_t* gap_us, const float* work,
     return fail(h, LBSIM_EINVAL, "lbsim_set_trace_bank needs arrival_source TRACE");
   if (gap_us == nullptr || work == nullptr || row_begin == nullptr)
     return fail(h, LBSIM_EINVAL, "trace bank: need device gap_us / work and host row_begin");
+  if (h->ack_max > 0 && n_traces > 1)
+    return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "a trace bank");
   if (n_traces < 1 || n_traces > 4096)
     return fail(h, LBSIM_EINVAL, "trace bank: n_traces must be in [1, 4096] (got %d)", n_traces);
   if (row_begin[0] != 0) return fail(h, LBSIM_EINVAL, "trace bank: row_begin[0] must be 0");
@@ -1728,6 +1750,7 @@ int lbsim_set_trace_schedule(lbsim_t* h, const int32_t* trace_id, int rows, int 
                              int steps_per_phase, int wrap, void* stream) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "a trace schedule");
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "a trace schedule");
   if (!h->prm.trace)
     return fail(h, LBSIM_EINVAL, "a trace schedule needs arrival_source TRACE");
   if (h->bank_begin.empty())
@@ -1840,6 +1863,7 @@ int lbsim_set_workload_tables(lbsim_t* h, const float* tables, int n_tables, con
                               const int32_t* work_id, int rows, void* stream) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "workload tables");
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "workload tables");
   if (h->prm.trace)
     return fail(h, LBSIM_EINVAL, "workload tables on a TRACE handle: the trace supplies gap and "
                                  "work");
@@ -2124,6 +2148,7 @@ int lbsim_rate_phase(lbsim_t* h, int32_t* phase_out, void* stream) {
 int lbsim_flow_stats_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "flow statistics");
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "flow statistics");
   if (h->flow_buf != nullptr) return LBSIM_OK;
   if (h->reset_seen)
     return fail(h, LBSIM_EINVAL, "lbsim_flow_stats_enable must precede the handle's first "
@@ -2151,6 +2176,7 @@ int lbsim_cross_traffic_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "cross traffic");
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "cross traffic");
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "cross traffic");
   if (h->cross_buf != nullptr) return LBSIM_OK;
   if (h->prm.lf_thr != 0u)
     return fail(h, LBSIM_ENOTSUP, "cross traffic on a lost-FIN handle (lost_fin_prob > 0): the "
@@ -2258,6 +2284,7 @@ int lbsim_server_workers_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "server workers");
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "server workers");
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "server workers");
   if (h->workers_buf != nullptr) return LBSIM_OK;
   if (h->prm.lf_thr != 0u)
     return fail(h, LBSIM_ENOTSUP, "server workers on a lost-FIN handle (lost_fin_prob > 0): the "
@@ -2436,6 +2463,7 @@ int server_pool_enable(lbsim_t* h, int32_t balancers, bool ps) {
     return fail(h, LBSIM_EINVAL, "server pools are already on with balancers = %d", (int)h->pool.A);
   }
   if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "server pools");
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "server pools");
   // what the pool kernel has no code for (marllb_amd/pools.py check_pool_config states the
   // config's and the constructor's part of this list, with the same words, before a handle
   // exists: keep the two together; tests/test_server_pools.py walks both)
@@ -2495,6 +2523,7 @@ int lbsim_server_pool_size(const lbsim_t* h) { return h == nullptr ? 0 : (int)h-
 int lbsim_processor_sharing_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->ps) return LBSIM_OK;
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "processor sharing");
   // what the PS kernel has no code for (marllb_amd/ps.py check_ps_config states the config's and
   // the constructor's part of this list, with the same words, before a handle exists: keep the
   // two together; tests/test_processor_sharing.py walks both)
@@ -2523,6 +2552,109 @@ int lbsim_processor_sharing_enable(lbsim_t* h) {
 }
 
 int lbsim_processor_sharing(const lbsim_t* h) { return h != nullptr && h->ps ? 1 : 0; }
+
+// ---- duration samples at every data ACK (the rule: lbsim_acks.h, the kernel:
+//      lbsim_dyn_ack.hip)
+namespace {
+const char kAckOff[] = "%s: ack samples are off: call lbsim_ack_samples_enable first";
+}  // namespace
+
+int lbsim_ack_samples_enable(lbsim_t* h, int32_t max_acks) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (!ack_max_ok(max_acks))
+    return fail(h, LBSIM_EINVAL, "ack samples: max_acks must be in [1, %d] (got %d)",
+                (int)kAckMaxAcks, (int)max_acks);
+  if (h->ack_max > 0) {
+    if (max_acks == h->ack_max) return LBSIM_OK;
+    return fail(h, LBSIM_EINVAL, "ack samples are already on with max_acks = %d", (int)h->ack_max);
+  }
+  // what the ACK kernel has no code for, or what its model does not cover (marllb_amd/acks.py
+  // check_ack_config states the config's and the constructor's part of this list, with the same
+  // words, before a handle exists: keep the two together; tests/test_ack_samples.py walks both)
+  const char* no = nullptr;
+  const lbsim_config_t& c = h->cfg;
+  if (c.lost_fin_prob > 0.0f) no = "lost_fin_prob > 0";
+  else if (c.fail_prob > 0.0f) no = "fail_prob > 0";
+  else if (c.duration_mode == LBSIM_DURATION_SERVICE) no = "duration_mode SERVICE";
+  else if (c.reservoir_mode == LBSIM_RESERVOIR_VPP) no = "reservoir_mode VPP";
+  else if (c.n_flow_on_mode == LBSIM_NFLOW_VPP) no = "n_flow_on_mode VPP";
+  else if (c.next_step_reset != 0) no = "next_step_reset";
+  else if (h->avail_on) no = "server availability";
+  else if (h->cross_buf != nullptr) no = "cross traffic";
+  else if (h->workers_buf != nullptr) no = "server workers";
+  else if (h->delay_buf != nullptr) no = "action delay";
+  else if (h->pool.A > 0) no = "server pools";
+  else if (h->ps) no = "processor sharing";
+  else if (h->flow_buf != nullptr) no = "flow statistics";
+  else if (h->wtab_T > 0) no = "workload tables";
+  else if (h->bank_begin.size() > 2) no = "a trace bank";
+  else if (h->tsel_P > 0) no = "a trace schedule";
+  if (no != nullptr) return fail(h, LBSIM_ENOTSUP, "ack samples with %s: not supported", no);
+  if (h->reset_seen)
+    return fail(h, LBSIM_EINVAL, "lbsim_ack_samples_enable must precede the handle's first "
+                                 "lbsim_reset (it adds state sections and changes which kernels "
+                                 "the handle launches)");
+  DeviceGuard g(h->device);
+  // the duration reservoir's {us, ts} records and its count (zeroed), and the intervals
+  const size_t BS = (size_t)h->B * h->S;
+  const size_t bytes[3] = {BS * K * 8, BS * 4, (size_t)h->B * 4};
+  void* p[3] = {nullptr, nullptr, nullptr};
+  bool ok = true;
+  for (int i = 0; i < 3 && ok; ++i)
+    ok = hipMalloc(&p[i], bytes[i]) == hipSuccess && hipMemset(p[i], 0, bytes[i]) == hipSuccess;
+  std::vector<int32_t> us((size_t)h->B, kAckDefaultInterval);
+  ok = ok && hipMemcpy(p[2], us.data(), bytes[2], hipMemcpyHostToDevice) == hipSuccess &&
+       hipDeviceSynchronize() == hipSuccess;
+  if (!ok) {
+    for (void* q : p)
+      if (q != nullptr) (void)hipFree(q);
+    return fail(h, LBSIM_ENOMEM, "ack samples: device allocation failed");
+  }
+  for (void* q : p) h->allocs.push_back(q);
+  h->st.res_dur = (uint32_t*)p[0];
+  h->st.res_count_dur = (uint32_t*)p[1];
+  h->ack_us = (int32_t*)p[2];
+  h->ack_max = max_acks;
+  h->plan = plan_of(h);  // the ACK dynamics and the general observe (make_plan)
+  return LBSIM_OK;
+}
+
+int lbsim_ack_samples(const lbsim_t* h) { return h != nullptr ? (int)h->ack_max : 0; }
+
+int lbsim_set_ack_interval(lbsim_t* h, const int32_t* us, int rows) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->ack_max == 0) return fail(h, LBSIM_ENOTSUP, kAckOff, "lbsim_set_ack_interval");
+  if (us == nullptr) return fail(h, LBSIM_EINVAL, "ack interval: us is NULL");
+  if (rows != 1 && rows != h->B)
+    return fail(h, LBSIM_ESHAPE, "ack interval: rows must be 1 or num_envs = %d (got %d)", h->B,
+                rows);
+  for (int i = 0; i < rows; ++i)
+    if (!ack_interval_ok(us[i]))  // the device array is untouched: the previous intervals stay
+      return fail(h, LBSIM_EINVAL, "ack interval: us[%d] = %d is not in [1, 2^30]", i, (int)us[i]);
+  std::vector<int32_t> v((size_t)h->B);
+  for (int b = 0; b < h->B; ++b) v[(size_t)b] = us[rows == 1 ? 0 : b];
+  DeviceGuard g(h->device);
+  if (hipMemcpy(h->ack_us, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "ack interval: hipMemcpy H2D failed");
+  return LBSIM_OK;
+}
+
+int lbsim_get_ack_interval(lbsim_t* h, int32_t* us_out) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->ack_max == 0) return fail(h, LBSIM_ENOTSUP, kAckOff, "lbsim_get_ack_interval");
+  if (us_out == nullptr) return fail(h, LBSIM_EINVAL, "ack interval: us_out is NULL");
+  DeviceGuard g(h->device);
+  if (hipMemcpy(us_out, h->ack_us, (size_t)h->B * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(h, LBSIM_EDEVICE, "ack interval: hipMemcpy D2H failed");
+  return LBSIM_OK;
+}
+
+int lbsim_clear_ack_interval(lbsim_t* h) {
+  if (h == nullptr) return LBSIM_EINVAL;
+  if (h->ack_max == 0) return fail(h, LBSIM_ENOTSUP, kAckOff, "lbsim_clear_ack_interval");
+  const int32_t us = kAckDefaultInterval;
+  return lbsim_set_ack_interval(h, &us, 1);
+}
 
 // ---- cores of processor-sharing servers (the rule: lbsim_ps.h; the conversion
 //      is lbsim_workers.h's kernel: the same range, the same offender count)
@@ -2728,6 +2860,7 @@ int lbsim_action_delay_enable(lbsim_t* h, int32_t max_delay_steps) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "action delay");
   if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "action delay");
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "action delay");
   if (!delay_steps_ok(max_delay_steps))
     return fail(h, LBSIM_EINVAL, "action delay: max_delay_steps must be in [1, %d] (got %d)",
                 (int)kMaxDelaySteps, (int)max_delay_steps);
@@ -2831,6 +2964,7 @@ int lbsim_server_avail_enable(lbsim_t* h) {
   if (h == nullptr) return LBSIM_EINVAL;
   if (h->pool.A > 0) return fail(h, LBSIM_ENOTSUP, kPoolNoCompose, "server availability");
   if (h->ps) return fail(h, LBSIM_ENOTSUP, kPsNoCompose, "server availability");
+  if (h->ack_max > 0) return fail(h, LBSIM_ENOTSUP, kAckNoCompose, "server availability");
   if (h->avail_on) return LBSIM_OK;
   if (h->prm.fail_thr != 0u)
     return fail(h, LBSIM_ENOTSUP, "scripted availability on a handle with random failures "

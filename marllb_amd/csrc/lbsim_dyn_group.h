@@ -29,6 +29,7 @@
 // [slot][lane].
 #pragma once
 
+#include "lbsim_acks.h"
 #include "lbsim_cross.h"
 #include "lbsim_delay.h"
 #include "lbsim_kernels.h"
@@ -184,6 +185,14 @@ struct DelayLane {
   float w2 = 1.0f;
 };
 
+// Duration samples at every data ACK (lbsim_acks.h) as a lane of
+// dynamics_group_ack_kernel sees them (the ACK instantiations alone): its env's interval and the
+// handle's max_acks.
+struct AckLane {
+  int32_t us = kAckDefaultInterval;
+  int32_t max_acks = kAckDefaultMax;
+};
+
 // The lane's queue by position from the head (lbsim_workers.h's accessor): the LDS window below
 // kGroupWL, the HBM ring from there on.  Window and ring accesses stay in separate branches, the
 // ring's fenced as at the push site: no flat access (see dynamics_kernel).
@@ -304,6 +313,50 @@ __device__ __forceinline__ void split_complete(const DevState& st, const SimPara
   else
     split_add(st, p, V, sb, gid, episode, s, false, (uint32_t)(tc - ta), ts_ms, has_r, r);
 }
+// ---- duration samples at every data ACK: the fct reservoir keeps its count,
+//      slots and draws -- the arrival's word in-step, the reservoir stream under word (2 << 24) | s
+//      for carried flows -- so it is bit for bit a plain handle's; the duration reservoir has its
+//      own count and {us, ts} records and draws every sample from the reservoir stream under a
+//      word of its own, bit 17.  (The reverse of the lost-FIN split above, where the duration side
+//      keeps the unsplit draws and the fct side moves to bit 16.)
+constexpr uint32_t kAckStreamBit = 1u << 17;
+// One ACK's sample into the duration reservoir of server row sb (as split_add's carried form: the
+// big flag at the store, the slot marked in chg).
+__device__ __forceinline__ void ack_add(const DevState& st, const SimParams& p, SrvLane& V,
+                                        uint32_t sb, uint32_t gid, uint32_t episode, int s,
+                                        uint32_t v, uint32_t ts_ms) {
+  const uint32_t c = V.rcnt_d;
+  int slot = (int)c;
+  if (c >= (uint32_t)K) {
+    const u32x4 d = philox4x32_10(
+        u32x4{c >> 1, gid, episode, (kStreamReservoir << 24) | kAckStreamBit | (uint32_t)s},
+        p.key0, p.key1);
+    slot = reservoir_slot(c, d);
+  }
+  if (slot >= 0) {
+    if (v >= kPackLimit) V.big = true;
+    reinterpret_cast<uint2*>(st.res_dur)[(size_t)sb * K + (uint32_t)slot] = make_uint2(v, ts_ms);
+    atomicOr(V.chgw + ((uint32_t)slot >> 5) * 64u, 1u << (slot & 31));
+  }
+  V.rcnt_d = count_inc(c);
+}
+// The ACKs in (0, dt] of the flow that arrived at ta, starts service at t0 and completes at tc
+// (relative us), in time order: the first and the last j of the window (lbsim_acks.h), no trip
+// when it holds none.  The ACKs at or before 0 were recorded by earlier steps.
+__device__ __forceinline__ void ack_flow(const DevState& st, const SimParams& p, SrvLane& V,
+                                         uint32_t sb, uint32_t gid, uint32_t episode, int s,
+                                         const AckLane& ak, int32_t ta, int32_t t0, int32_t tc,
+                                         int32_t dt, uint32_t base_ms, uint32_t base_rem) {
+  if (t0 >= dt) return;
+  const int32_t svc = tc - t0;
+  const int32_t k = ack_count(svc, ak.us, ak.max_acks);
+  int32_t jlo, jhi;
+  ack_window(t0, svc, k, 0, dt, jlo, jhi);
+  for (int32_t j = jlo; j <= jhi; ++j) {
+    const int32_t t = ack_time(t0, svc, k, j);  // in (0, dt]
+    ack_add(st, p, V, sb, gid, episode, s, (uint32_t)(t - ta), base_ms + (base_rem + (uint32_t)t) / 1000u);
+  }
+}
 // reservoir_mode VPP: the server's bins zeroed (reset, failure; VPP's zeroed shm).
 __device__ __forceinline__ void vpp_zero_bins(const DevState& st, const SimParams& p, uint32_t sb) {
   uint4* r4 = reinterpret_cast<uint4*>(st.res + (size_t)sb * K);
@@ -349,7 +402,8 @@ __device__ __forceinline__ GroupConst group_const(const SimParams& p, float mean
 // VPP, exact flow statistics (fs_on), workload tables (ws) -- compiled only into
 // dynamics_group_full_kernel, so none of their registers weigh on the plain kernel (126 VGPRs, 4
 // waves per SIMD; with them inlined it took 164).
-template <int G, int POLICY, bool TRACE, bool FAST, bool FULL = false, bool DELAY = false>
+template <int G, int POLICY, bool TRACE, bool FAST, bool FULL = false, bool DELAY = false,
+          bool ACK = false>
 __device__ __forceinline__ void group_event_loop(const DevState& st, const SimParams& p,
                                                  LaneState<1>& E, SrvLane& V, int s, int gbase,
                                                  int n_alias, const GroupConst& gc, int2* win,
@@ -359,7 +413,8 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
                                                  const WorkSel& ws = WorkSel{},
                                                  const CrossLane& cx = CrossLane{},
                                                  const WorkLane& wk = WorkLane{},
-                                                 DelayLane dl = DelayLane{}) {
+                                                 DelayLane dl = DelayLane{},
+                                                 const AckLane& ak = AckLane{}) {
   constexpr int WL = kGroupWL;
   constexpr bool two_choice = (POLICY == 1 || POLICY == 3);
   constexpr bool alias = POLICY == kPolicyAlias;
@@ -449,6 +504,16 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
                  lf_lost(p, gc.base_ms * 1000u + gc.base_rem + (uint32_t)wslot(V.lh)->y, E.gid,
                          E.episode)) {
         V.lost += 1;
+      }
+    }
+    if constexpr (ACK) {
+      // ACK samples (§3.25): the popped flow's ACKs of this step, before its window slot is taken
+      // over.  Its service began at max(ta, its predecessor's tc), which V.last still holds; pops
+      // of a server come in FIFO order, so its samples enter in time order.
+      if (due) {
+        const int32_t eta = wslot(V.lh)->y;
+        ack_flow(st, p, V, (uint32_t)((size_t)(my_res - st.res) / K), E.gid, E.episode, s, ak, eta,
+                 eta > V.last ? eta : V.last, V.head_tc, dt, gc.base_ms, gc.base_rem);
       }
     }
     if (due && V.cnt > WL) {  // rare: the slot the pop frees takes queue entry WL from the ring
@@ -581,7 +646,8 @@ __device__ __forceinline__ void group_event_loop(const DevState& st, const SimPa
       // lost-FIN flows only on split handles: fct = tc - ta here
       const uint32_t fct = (uint32_t)(tc_a - ta);
       my_res[(uint32_t)slot] = make_uint2(fct, gc.base_ms + (gc.base_rem + (uint32_t)tc_a) / 1000u);
-      if constexpr (FULL) {  // the duration plane:
+      if constexpr (FULL && !ACK) {  // the duration plane (an ACK handle's res_dur holds its
+        // duration reservoir's records instead, written by ack_add alone):
         if (st.res_dur != nullptr)  // the age tc - ta, or the service time svc = tc - start
           st.res_dur[(size_t)(my_res - st.res) + (uint32_t)slot] =
               p.dur_service ? (uint32_t)svc : (uint32_t)(tc_a - ta);
@@ -873,7 +939,7 @@ __device__ __forceinline__ void group_count_loop(const DevState& st, const SimPa
   V.last = lastdone;
 }
 
-template <int G, int POLICY, bool TRACE, bool FULL = false, bool DELAY = false>
+template <int G, int POLICY, bool TRACE, bool FULL = false, bool DELAY = false, bool ACK = false>
 __device__ __forceinline__ void sim_step_group(const DevState& st, const SimParams& p,
                                                LaneState<1>& E, SrvLane& V, uint32_t b, int s,
                                                int gbase, float w_own, const float (&wall)[G],
@@ -882,7 +948,8 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
                                                const TraceSel& ts = TraceSel{},
                                                const CrossLane& cx = CrossLane{},
                                                const WorkLane& wk = WorkLane{},
-                                               const DelayLane& dl = DelayLane{}) {
+                                               const DelayLane& dl = DelayLane{},
+                                               const AckLane& ak = AckLane{}) {
   constexpr int WL = kGroupWL;
   const int S = p.S, Q = p.Q;
   const int32_t dt = p.dt_us;
@@ -977,8 +1044,12 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
           const uint32_t fct = (uint32_t)(etc - eta);
           const uint32_t dur = FULL ? dur_sample(p, etc, eta, eta > prev ? eta : prev) : fct;
           V.big |= big_record(fct, dur);
-          store_record(st, (size_t)sb * K + (uint32_t)slot, fct, dur,
-                       base_ms + (base_rem + (uint32_t)etc) / 1000u);
+          if constexpr (ACK)  // (no duration plane: res_dur is the duration reservoir's records)
+            st.res[(size_t)sb * K + (uint32_t)slot] =
+                make_uint2(fct, base_ms + (base_rem + (uint32_t)etc) / 1000u);
+          else
+            store_record(st, (size_t)sb * K + (uint32_t)slot, fct, dur,
+                         base_ms + (base_rem + (uint32_t)etc) / 1000u);
           mark(slot);
         }
         rc = count_inc(rc);
@@ -1021,9 +1092,19 @@ __device__ __forceinline__ void sim_step_group(const DevState& st, const SimPara
   const bool finite = lsq || alias || !V.act ||
                       (fabs(V.den) >= 1e-30 && fabs(V.den) <= 1e300);  // false for NaN
   if constexpr (FULL) {  // (a full handle always runs the general loop)
-    group_event_loop<G, POLICY, TRACE, false, true, DELAY>(st, p, E, V, s, gbase, n_alias, gc, win,
-                                                           atab, acache, my_res, my_ring, fs_on,
-                                                           ts, ws, cx, wk, dl);
+    group_event_loop<G, POLICY, TRACE, false, true, DELAY, ACK>(st, p, E, V, s, gbase, n_alias, gc,
+                                                                win, atab, acache, my_res, my_ring,
+                                                                fs_on, ts, ws, cx, wk, dl, ak);
+    if constexpr (ACK) {
+      // ACK samples (§3.25): after the step's last pop the head flow may be in service already;
+      // its ACKs due by dt enter the reservoir before observe runs (it completes after dt: the
+      // rest follow in later steps, from the same t0 = max(ta, last_tc) rebased)
+      if (V.act && V.cnt > 0) {
+        const int32_t eta = wslot(V.lh)->y;
+        ack_flow(st, p, V, sb, E.gid, E.episode, s, ak, eta, eta > V.last ? eta : V.last,
+                 V.head_tc, dt, base_ms, base_rem);
+      }
+    }
     // split handles: the guesses due by the step's end (oracle sim_step)
     if (p.split && V.act) split_flush(st, p, V, sb, E.gid, E.episode, s, dt, base_us);
   } else if constexpr (!COUNT) {
@@ -1081,7 +1162,8 @@ struct DynGroupLds {
 // One step (or reset) of the 64 / G envs of wave `wave` (env b = wave * 64 / G + lane / G), lane s
 // of a group owning server s: state in, the event loop, state back to HBM.  Lanes of envs past B
 // (or outside the reset mask) return at once, whole groups together.
-template <int G, int MODE, int POLICY, bool TRACE, bool FULL = false, bool DELAY = false>
+template <int G, int MODE, int POLICY, bool TRACE, bool FULL = false, bool DELAY = false,
+          bool ACK = false>
 __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimParams& p,
                                                const void* action, int action_dtype,
                                                int32_t* assign_out, const uint8_t* reset_mask,
@@ -1089,7 +1171,8 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
                                                const FlowStats& fs = FlowStats{},
                                                const CrossTraffic& ct = CrossTraffic{},
                                                const ServerWorkers& sw = ServerWorkers{},
-                                               const ActionDelay& ad = ActionDelay{}) {
+                                               const ActionDelay& ad = ActionDelay{},
+                                               const AckSamples& as = AckSamples{nullptr, 0}) {
   static_assert(G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64,
                 "group = a power of two lanes of the wave");
   constexpr int WL = kGroupWL;
@@ -1155,6 +1238,12 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
       wk.on = true;
       wk.c = V.act ? sw.c[sb] : 1;
     }
+  }
+
+  AckLane ak;  // ACK samples: the env's interval, read once
+  if constexpr (ACK) {
+    ak.us = as.us[b];
+    ak.max_acks = as.max_acks;
   }
 
   auto reset_in = [&]() {  // a new episode (env.py:186-213): its first arrival, empty servers
@@ -1231,6 +1320,7 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
         V.pcnt = (int32_t)(ph >> 16);
         if (V.pcnt > 0) V.pdue = st.pend[(size_t)sb * (uint32_t)p.pend_P + (uint32_t)V.phead].x;
       }
+      if constexpr (ACK) V.rcnt_d = st.res_count_dur[sb];  // the duration reservoir's own count
       if (fs.hist != nullptr) {  // flow statistics: this step's completions count
         V.fs_row = fs.hist + (size_t)sb * kFlowBins;
         V.fs_cnt = fs.count[sb];
@@ -1323,14 +1413,15 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     load_in();
     cross_in();
     delay_in();
-    sim_step_group<G, POLICY, TRACE, FULL, DELAY>(st, p, E, V, b, s, gbase, w_own, wall, win,
-                                                  atab, acache, fs_on, ts, cx, wk, dl);
+    sim_step_group<G, POLICY, TRACE, FULL, DELAY, ACK>(st, p, E, V, b, s, gbase, w_own, wall, win,
+                                                       atab, acache, fs_on, ts, cx, wk, dl, ak);
   } else if constexpr (MODE == kModeReset) {
     reset_in();
     cross_in();
-    for (int k = 0; k < p.warmup_steps; ++k)
-      sim_step_group<G, POLICY, TRACE, FULL>(st, p, E, V, b, s, gbase, 1.0f, wall, win, atab,
-                                             acache, fs_on, ts, cx, wk);
+    for (int k = 0; k < p.warmup_steps; ++k)  // (ACK: the warm-up records its ACKs too)
+      sim_step_group<G, POLICY, TRACE, FULL, false, ACK>(st, p, E, V, b, s, gbase, 1.0f, wall, win,
+                                                         atab, acache, fs_on, ts, cx, wk,
+                                                         DelayLane{}, ak);
     reset_out(0);
   } else {
     // kModeStepNR (next-step auto-reset): an env whose last step returned done resets in place of
@@ -1349,8 +1440,8 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
     const int nsteps = rs ? p.warmup_steps : 1;
     const float w = rs ? 1.0f : w_own;
     for (int k = 0; k < nsteps; ++k)
-      sim_step_group<G, POLICY, TRACE, FULL, DELAY>(st, p, E, V, b, s, gbase, w, wall, win, atab,
-                                                    acache, fs_on, ts, cx, wk, dl);
+      sim_step_group<G, POLICY, TRACE, FULL, DELAY, ACK>(st, p, E, V, b, s, gbase, w, wall, win,
+                                                         atab, acache, fs_on, ts, cx, wk, dl, ak);
     if (rs) reset_out(-1);
   }
 
@@ -1373,6 +1464,7 @@ __device__ __forceinline__ void dyn_group_wave(const DevState& st, const SimPara
       st.res_count_dur[sb] = V.rcnt_d;
       st.pend_hc[sb] = (uint32_t)V.phead | ((uint32_t)V.pcnt << 16);
     }
+    if constexpr (ACK) st.res_count_dur[sb] = V.rcnt_d;
     st.hc[sb] = (uint32_t)V.head | (V.big ? kHcBig : 0u) | ((uint32_t)V.cnt << 16);
     st.last_tc[sb] = V.last;
     st.res_count[sb] = V.rcnt;
@@ -1446,6 +1538,22 @@ __global__ void __launch_bounds__(64)
   dyn_group_wave<G, MODE, POLICY, TRACE, true, true>(st, p, action, action_dtype, assign_out,
                                                      reset_mask, blockIdx.x, (int)threadIdx.x, L,
                                                      fs, ct, sw, ad);
+}
+
+// The full form with duration samples at every data ACK (as: the envs' ACK
+// intervals and max_acks), for the steps and the resets of an enabled handle (a reset's warm-up
+// records its ACKs too).  Instantiations of their own (lbsim_dyn_ack.hip), as the delay form's: no
+// other kernel carries the ACK code.  An ACK handle has none of the other full-form options, so
+// the flow statistics, the cross traffic and the worker counts are the null ones.
+template <int G, int MODE, int POLICY, bool TRACE>
+__global__ void __launch_bounds__(64)
+    dynamics_group_ack_kernel(DevState st, SimParams p, const void* action, int action_dtype,
+                              int32_t* assign_out, const uint8_t* reset_mask, AckSamples as) {
+  static_assert(MODE != kModeStepNR, "next-step auto-reset is refused on an ACK handle");
+  __shared__ DynGroupLds<POLICY> L;
+  dyn_group_wave<G, MODE, POLICY, TRACE, true, false, true>(
+      st, p, action, action_dtype, assign_out, reset_mask, blockIdx.x, (int)threadIdx.x, L,
+      FlowStats{}, CrossTraffic{}, ServerWorkers{}, ActionDelay{}, as);
 }
 
 }  // namespace lbk

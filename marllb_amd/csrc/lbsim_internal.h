@@ -8,6 +8,9 @@
 //                      (host-only; the launchers below turn the plan into template arguments)
 //   lbsim_dyn_delay.hip  dynamics_group_delay_kernel launchers (action latency); built twice
 //                      (-DLBSIM_DYN_MODE=0 step, 2 step_nr)
+//   lbsim_acks.h       duration samples at every data ACK: the host / device rule of a flow's ACKs
+//   lbsim_dyn_ack.hip  dynamics_group_ack_kernel launchers (ACK samples); built twice
+//                      (-DLBSIM_DYN_MODE=0 step, 1 reset)
 //   lbsim_pool.h       shared server pools: the host / device rule of a pool and its physical FIFOs
 //   lbsim_dyn_pool.hip  dynamics_pool_kernel launchers (shared server pools); built twice
 //                      (-DLBSIM_DYN_MODE=0 step, 1 reset, with the pool handle's two small kernels)
@@ -31,6 +34,7 @@
 #include <type_traits>
 
 #include "../../include/lbsim.h"
+#include "lbsim_acks.h"
 #include "lbsim_cross.h"
 #include "lbsim_delay.h"
 #include "lbsim_kernels.h"
@@ -99,6 +103,14 @@ void launch_dynamics_delay_step(const LaunchCtx& L, const void* action, int dtyp
                                 int32_t* assign, const uint8_t* mask, hipStream_t s);
 void launch_dynamics_delay_step_nr(const LaunchCtx& L, const void* action, int dtype,
                                    int32_t* assign, const uint8_t* mask, hipStream_t s);
+
+// The dynamics of a handle with duration samples at every data ACK (lbsim_dyn_ack.hip:
+// dynamics_group_ack_kernel; the plan is a full group one of kernel
+// LBSIM_DYN_KERNEL_ACK; as: the envs' ACK intervals and max_acks).
+void launch_dynamics_ack_step(const LaunchCtx& L, const AckSamples& as, const void* action,
+                              int dtype, int32_t* assign, hipStream_t s);
+void launch_dynamics_ack_reset(const LaunchCtx& L, const AckSamples& as, const uint8_t* mask,
+                               hipStream_t s);
 
 // The dynamics of a handle with shared server pools (lbsim_dyn_pool.hip: dynamics_pool_kernel; the
 // plan is a pool one and pa holds the physical FIFOs).  A reset's mask is the widened one.

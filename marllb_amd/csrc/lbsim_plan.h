@@ -67,6 +67,7 @@ struct PlanInput {
   int pool = 0;  // balancers per shared server pool (lbsim_server_pool_enable); 0: no pools
   bool ps = false;  // processor-sharing servers (lbsim_processor_sharing_enable)
   bool pool_ps = false;  // the pools' servers are processor-sharing ones (lbsim_server_pool_enable_ps)
+  bool ack_samples = false;  // duration samples at every data ACK (lbsim_ack_samples_enable)
 };
 
 enum StepForm { kStepWave, kStepGroupFused, kStepTwoLaunch };
@@ -83,6 +84,7 @@ constexpr unsigned env_lane_block(int maxs) { return maxs <= 8 ? 256u : 128u; }
 
 struct DynPlan {
   int kernel;   // lbsim_dyn_kernel: LBSIM_DYN_KERNEL_ENV_LANE | _GROUP | _WAVE | _POOL | _PS | _POOL_PS
+                // | _ACK
   int width;    // env-lane: MAXS 4 | 8 | 16; group: G lanes per env; wave: NG ring registers;
                 // pool: G lanes per pool; ps: G lanes per env
   bool full;    // group: dynamics_group_full_kernel (every feature's code, its own budget)
@@ -128,8 +130,9 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
   // Cross traffic: the hidden flows' decision, flag and count are compiled into the full form alone.
   // Multi-worker servers: so are the start rule and the sorted insert.
   // Action latency: so are the weight ring and the mid-step switch.
+  // ACK samples: so are the ACK inserts, in instantiations of their own.
   const bool full_only = in.res_vpp || in.flow_stats || in.work_tables || in.cross_traffic ||
-                         in.server_workers || in.action_delay;
+                         in.server_workers || in.action_delay || in.ack_samples;
   // Shared server pools: dynamics_pool_kernel for step and reset, one group of
   // pow2 >= max(S, A) lanes per pool (LBSIM_DYN_GROUP_LANES = 4 | 8 | 16 where it holds both), and
   // the ordinary two-launch observe: no wave kernel, no one-launch step.
@@ -208,6 +211,8 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
       else if (step && in.next_reset) d.waves = 4;
       else if (step && in.policy == LBSIM_POLICY_SED && (g == 4 || g == 8) && d.grid > 4 * simds)
         d.waves = 5;
+      // ACK samples: dynamics_group_ack_kernel, the full form's groups and grid
+      if (in.ack_samples) d.kernel = LBSIM_DYN_KERNEL_ACK;
     }
     return d;
   };
@@ -253,7 +258,8 @@ inline StepPlan make_plan(const PlanInput& in, const Overrides& ov) {
     // AGE, lost-FIN off) and 8 rows per wave: S <= 8 (8 / S whole envs per wave:
     // observe_pair_kernel), or S a multiple of 8 (S / 8 waves per env: observe_pair16_kernel,
     // observe_pair_chunks_kernel + observe_rows_kernel).
-    if (step && !in.dur_plane && (S <= 8 || S % 8 == 0)) {
+    // (ACK samples: the duration reservoir has records and a count of its own: the general observe)
+    if (step && !in.dur_plane && !in.ack_samples && (S <= 8 || S % 8 == 0)) {
       if (S <= 8) o = {kObsPair, 0, 0, 0u, blocks(B, 8 / S), 64u, 0u};
       else if (S == 16) o = {kObsPair16, 0, 0, 0u, (unsigned)B, 128u, 0u};
       else o = {kObsPairChunks, 64, S / 8, (unsigned)(B * (S / 8)), (unsigned)B, 64u, 0u};

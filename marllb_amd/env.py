@@ -559,6 +559,33 @@ class Handle:
         """Every count 1 (lbsim_clear_ps_cores), on the current stream."""
         self.check(self.lib.lbsim_clear_ps_cores(self.h, ctypes.c_void_p(self._stream())))
 
+    def enable_ack_samples(self, max_acks: int = 8) -> None:
+        """Duration samples at every data ACK from now on (lbsim_ack_samples_enable, DESIGN.md
+        §3.25): a flow offers its server's duration reservoir up to max_acks samples, one per data
+        ACK.  Before the handle's first reset; a second call with the same value is a no-op."""
+        self.check(self.lib.lbsim_ack_samples_enable(self.h, int(max_acks)))
+
+    def ack_samples(self) -> int:
+        """max_acks of an ACK-samples handle, else 0 (lbsim_ack_samples)."""
+        return int(self.lib.lbsim_ack_samples(self.h))
+
+    def set_ack_interval(self, us, *, rows: int) -> None:
+        """ACK intervals (lbsim_set_ack_interval): us (rows,) int32 contiguous host array of
+        microseconds, rows = 1 or B."""
+        self.check(self.lib.lbsim_set_ack_interval(
+            self.h, us.ctypes.data_as(ctypes.c_void_p), int(rows)))
+
+    def ack_interval(self):
+        """(B,) int32 host array: the ACK intervals in force, us (lbsim_get_ack_interval)."""
+        import numpy as np
+        out = np.empty(int(self.cfg.num_envs), np.int32)
+        self.check(self.lib.lbsim_get_ack_interval(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def clear_ack_interval(self) -> None:
+        """Every interval back to 1000 us (lbsim_clear_ack_interval)."""
+        self.check(self.lib.lbsim_clear_ack_interval(self.h))
+
     def ps_server_state(self, out) -> None:
         """The processor-sharing servers' privileged state into out, a contiguous (B, S, 4)
         float32 tensor on the handle's device (lbsim_ps_server_state): one kernel on the current
@@ -725,6 +752,8 @@ class DeviceSnapshot:
 
 _PS_CORES_OFF = ("{} on an env without processor-sharing servers: call "
                  "lbsim_processor_sharing_enable first (service_discipline=\"ps\")")
+_ACKS_OFF = ("{} on an env without ack samples: call lbsim_ack_samples_enable first "
+             "(ack_samples=True)")
 _POOL_PS_OFF = ("{} on an env without pools of processor-sharing servers: call "
                 "lbsim_server_pool_enable_ps first (pool_discipline=\"ps\")")
 
@@ -792,6 +821,16 @@ class VecLoadBalanceEnv:
     pool_ps_state() is the privileged view (ground_truth() is refused: LbsimError, code ENOTSUP).
     The default "fifo" is the pool above, untouched.
 
+    ack_samples=True records a duration sample at every data ACK, as the data plane does
+    (DESIGN.md §3.25): a flow offers its server's duration reservoir min(max_acks, max(1, svc //
+    ack_interval_us)) samples, its age at ACK times spread evenly over its service, instead of one
+    at its completion.  Columns 6-10 and the default reward then differ from the fct columns 1-5;
+    columns 0-5, the queues and the counters are bit for bit those of the env without the option.
+    max_acks in [1, 32]; ack_interval_us a scalar or (B,) of integer us (default 1000);
+    set_ack_interval / get_ack_interval / clear_ack_interval change and read it between steps.
+    The options the ACK dynamics have no code for are refused (LbsimError, code ENOTSUP;
+    marllb_amd.acks.check_ack_config states the rule).
+
     service_discipline="ps" makes every server a processor-sharing one: its one
     worker is shared equally by the flows queued on it, as an application host with more worker
     processes than cores shares its CPU, so a short flow is never stuck behind a long one and the
@@ -816,8 +855,13 @@ class VecLoadBalanceEnv:
                  cross_traffic: bool = False, server_workers=False, action_delay=False,
                  max_delay_steps: int = 1, balancers_per_pool: int = 0,
                  service_discipline: str = "fifo", ps_cores=None,
-                 pool_discipline: str = "fifo", pool_ps_cores=None, **kwargs):
+                 pool_discipline: str = "fifo", pool_ps_cores=None,
+                 ack_samples: bool = False, max_acks: int = 8, ack_interval_us=None, **kwargs):
         torch = _torch()
+        if ack_interval_us is not None and not ack_samples:  # before any device is touched
+            raise _lib.LbsimError(_lib.ENOTSUP, _ACKS_OFF.format("ack_interval_us"))
+        self.ack_samples = bool(ack_samples)
+        self.max_acks = int(max_acks) if ack_samples else 0
         if service_discipline not in ("fifo", "ps"):
             raise ValueError(f"Unknown service_discipline: {service_discipline}")
         if pool_discipline not in ("fifo", "ps"):
@@ -869,6 +913,16 @@ class VecLoadBalanceEnv:
                             action_delay=action_delay is not False and action_delay is not None,
                             balancers_per_pool=self.balancers_per_pool,
                             ps_cores=ps_cores is not None)
+        if ack_samples:  # the ACK rule on the config, before any device is touched
+            from .acks import check_ack_config
+            tr = kwargs.get("trace")
+            check_ack_config(self.cfg, max_acks=max_acks, flow_stats=flow_stats,
+                             server_availability=server_availability, cross_traffic=cross_traffic,
+                             server_workers=server_workers is not False and server_workers is not None,
+                             action_delay=action_delay is not False and action_delay is not None,
+                             balancers_per_pool=self.balancers_per_pool,
+                             service_discipline=service_discipline,
+                             trace_bank=tr is not None and _is_bank(tr))
         self.device_index = _device_index(device)
         self.device = torch.device("cuda", self.device_index)
         self.trace = kwargs.get("trace")
@@ -889,6 +943,10 @@ class VecLoadBalanceEnv:
             self.handle.enable_processor_sharing()
             if ps_cores is not None:
                 self.set_ps_cores(ps_cores)
+        if ack_samples:
+            self.handle.enable_ack_samples(max_acks)
+            if ack_interval_us is not None:
+                self.set_ack_interval(ack_interval_us)
         if flow_stats:
             self.handle.enable_flow_stats()
         self.server_availability = bool(server_availability)
@@ -1263,6 +1321,46 @@ class VecLoadBalanceEnv:
     def clear_server_workers(self) -> None:
         """Every server back to one worker."""
         self.handle.clear_server_workers()
+
+    # ---- duration samples at every data ACK (ack_samples=True; DESIGN.md §3.25)
+    def _acks_only(self, what: str) -> None:
+        if not self.ack_samples:
+            raise _lib.LbsimError(_lib.ENOTSUP, _ACKS_OFF.format(what))
+
+    def set_ack_interval(self, us) -> None:
+        """The envs' ACK intervals in integer microseconds, a scalar or (B,) in [1, 2^30], a
+        tensor or array on any device: a flow of svc us of service emits min(max_acks, max(1,
+        svc // interval)) data ACKs.  From the next launch on (step, reset, warm-up); a flow in
+        service then places its remaining ACKs by the new interval.  A value out of range, or a
+        non-integer one: ValueError, the previous intervals stay in force.  Not part of
+        get_state(); a shard passes its own rows.  graph_mode: the call copies into a device
+        array that never moves, so replays see it.
+        marllb_amd.randomize.sample_ack_interval draws per-env intervals."""
+        self._acks_only("set_ack_interval")
+        import numpy as np
+        torch = _torch()
+        B = self.num_envs
+        u = torch.as_tensor(us).detach().cpu()
+        if u.dim() == 0:
+            u = u.reshape(1)
+        if tuple(u.shape) not in ((1,), (B,)):
+            raise ValueError(f"ack interval: expected a scalar or shape ({B},), got {tuple(u.shape)}")
+        if u.dtype == torch.bool or (u.is_floating_point() and not bool((u == u.round()).all())):
+            raise ValueError("ack interval: expected integers")
+        # out-of-range values stay out of range as int32 (the library call rejects them)
+        a = np.ascontiguousarray(
+            u.to(torch.float64).clamp(-1.0, float((1 << 30) + 1)).numpy().astype(np.int32))
+        self.handle.set_ack_interval(a, rows=int(a.shape[0]))
+
+    def get_ack_interval(self):
+        """(B,) int32 device tensor: the ACK intervals in force, us (1000 until set)."""
+        self._acks_only("get_ack_interval")
+        return _torch().from_numpy(self.handle.ack_interval()).to(self.device)
+
+    def clear_ack_interval(self) -> None:
+        """Every env back to 1000 us."""
+        self._acks_only("clear_ack_interval")
+        self.handle.clear_ack_interval()
 
     # ---- cores of processor-sharing servers (service_discipline="ps"; DESIGN.md §3.23)
     def _ps_only(self, what: str) -> None:
@@ -2298,6 +2396,23 @@ class LoadBalanceEnv:
         """(S, 4) float32, columns marllb_amd.PS_STATE_COLUMNS (VecLoadBalanceEnv.ps_state of the
         one env)."""
         return self._ps_vec().ps_state()[0].cpu().numpy()
+
+    # ---- duration samples at every data ACK (LoadBalanceEnv(ack_samples=True, max_acks=8,
+    #      ack_interval_us=1000))
+    def _acks_vec(self) -> "VecLoadBalanceEnv":
+        if self._vec is None:
+            raise RuntimeError("ack samples need the GPU simulator (not reference_plumbing)")
+        return self._vec
+
+    def set_ack_interval(self, us: int) -> None:
+        """The env's ACK interval in integer us (VecLoadBalanceEnv.set_ack_interval)."""
+        self._acks_vec().set_ack_interval(us)
+
+    def get_ack_interval(self) -> int:
+        return int(self._acks_vec().get_ack_interval()[0].item())
+
+    def clear_ack_interval(self) -> None:
+        self._acks_vec().clear_ack_interval()
 
     # ---- action latency (LoadBalanceEnv(action_delay=0.02 or True))
     def _delay_vec(self) -> "VecLoadBalanceEnv":

@@ -120,6 +120,17 @@ class MultiAgentLoadBalanceEnv:
     def clear_action_delay(self) -> None:
         self.env.clear_action_delay()
 
+    def set_ack_interval(self, us: int) -> None:
+        """The env's ACK interval in integer us: LoadBalanceEnv.set_ack_interval (an env made with
+        ack_samples=True)."""
+        self.env.set_ack_interval(us)
+
+    def get_ack_interval(self) -> int:
+        return self.env.get_ack_interval()
+
+    def clear_ack_interval(self) -> None:
+        self.env.clear_ack_interval()
+
     def set_ps_cores(self, cores) -> None:
         """The servers' core counts, (total_servers,) in agent order: LoadBalanceEnv.set_ps_cores
         (an env made with service_discipline="ps")."""
@@ -301,6 +312,17 @@ class VecMultiAgentLoadBalanceEnv:
     def ps_state(self, out=None):
         """(B, S, 4) f32, columns marllb_amd.PS_STATE_COLUMNS: VecLoadBalanceEnv.ps_state."""
         return self.vec.ps_state(out)
+
+    def set_ack_interval(self, us) -> None:
+        """Per-env ACK interval in integer us, a scalar or (B,): VecLoadBalanceEnv.set_ack_interval
+        (an env made with ack_samples=True)."""
+        self.vec.set_ack_interval(us)
+
+    def get_ack_interval(self):
+        return self.vec.get_ack_interval()
+
+    def clear_ack_interval(self) -> None:
+        self.vec.clear_ack_interval()
 
     def set_action_delay(self, seconds) -> None:
         """Per-env control delay in seconds, a scalar or (B,): VecLoadBalanceEnv.set_action_delay

@@ -328,6 +328,30 @@ def sample_action_delay(num_envs: int, low: float = 0.0, high: float = 0.25, see
     return d.to(device=device, dtype=torch.float32).contiguous()
 
 
+# ---- ACK intervals (VecLoadBalanceEnv.set_ack_interval)
+
+
+def sample_ack_interval(num_envs: int, lo_us: int = 250, hi_us: int = 4000, seed: int = 0, *,
+                        device=None):
+    """-> (B,) int32 microseconds for VecLoadBalanceEnv.set_ack_interval: each env's ACK interval,
+    log-uniform over [lo_us, hi_us] (1 <= lo_us <= hi_us <= 2^30), rounded to whole us and kept
+    inside the bounds.  Deterministic for a seed."""
+    import math
+
+    import torch
+
+    B = int(num_envs)
+    if B < 1:
+        raise ValueError(f"need num_envs >= 1 (got {num_envs})")
+    lo, hi = int(lo_us), int(hi_us)
+    if lo != lo_us or hi != hi_us or not 1 <= lo <= hi <= 1 << 30:
+        raise ValueError(f"need integers 1 <= lo_us <= hi_us <= 2^30 (got {lo_us}, {hi_us})")
+    g = torch.Generator().manual_seed(int(seed))
+    u = torch.rand(B, generator=g, dtype=torch.float64)
+    v = torch.exp(math.log(lo) + (math.log(hi) - math.log(lo)) * u).round().clamp(lo, hi)
+    return v.to(device=device, dtype=torch.int32).contiguous()
+
+
 def sample_pool_arrival_rates(num_pools: int, num_balancers: int, total=(200.0, 400.0),
                               skew=(1.0, 1.0), seed: int = 0, *, generator=None, device=None):
     """-> (num_pools * num_balancers,) float32 flows/s for set_rates(arrival_rate=...) of an env
